@@ -15,7 +15,11 @@ rate of the same switch (configs[1] to the letter: one replica on one GPU) is me
 per switch).  Every chain starts from its own state (--decorrelate steps at set-up; --same-start for the common start of
 rounds 1-4).  --md-steps N times the reference's FULL iteration instead (NCMC switch + MD leg on the unfrozen System).
 
-    python bench.py --gpus N --steps K --warmup W [--replicas R]
+A plain run sets up, warms up, times the K steps and prints the line; --full adds everything else the line can carry: the
+single-chain rate, the CPU baseline, the nonbonded kernel timed in the stepping loop and alone, and the roofline block.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
+    python bench.py --gpus N --steps K --warmup W [--replicas R] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -330,6 +334,29 @@ def memory_use():
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, records, drivers, rank):
+    """--dump-outputs: what the last timed step computed, as float64 DIR/<name>.npy.  accept_records: what the step returns for every
+    chain of every rank ([accept, iteration, log_accept, protocol_work, correction], bench.py _record); positions / velocities: the
+    mobile atoms of this rank's chains as each chain carries them on (after the Metropolis test and the reset; the MD contexts' with
+    --md-steps), (chains, mobile atoms, 3) in nm and nm/ps.  More chains than DUMP_BUDGET_BYTES hold: a fixed seeded sample of them,
+    in chain order; chain_index names the chains kept (global chain indices)."""
+    records = np.asarray(records, dtype=np.float64)
+    batches = [d._md_batch or d._ncmc_batch for d in drivers]
+    mobile = np.nonzero(np.asarray(batches[0].engines[0].system.mass) > 0)[0]
+    R = sum(len(b) for b in batches)
+    per_chain = 2 * 3 * 8 * len(mobile)
+    keep = int(min(R, max(1, (DUMP_BUDGET_BYTES - records.nbytes) // per_chain)))
+    chosen = np.arange(R) if keep == R else np.sort(np.random.RandomState(20240).choice(R, keep, replace=False))
+    x = np.concatenate([b.read_atoms_all(mobile, kind=1) for b in batches])[chosen]
+    v = np.concatenate([b.read_atoms_all(mobile, kind=2) for b in batches])[chosen]
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("accept_records", records), ("chain_index", rank * R + chosen), ("positions", x), ("velocities", v)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _free_port():
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()
@@ -429,8 +456,13 @@ def main():
                     "or gloo (the accept records travel through host memory: what a one-GPU box can run)")
     ap.add_argument("--same-device", action="store_true", help="every rank uses GPU 0 (with --backend gloo: the whole N-rank path with real engines on a one-GPU box; "
                     "a correctness run -- the ranks share the device, `value` says nothing about scaling)")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="skip the stand-alone launches of the nonbonded kernel at the end (counter-collection runs: "
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the stand-alone launches of the nonbonded kernel at the end (counter-collection runs: "
                     "every launch of the kernel in the trace is then one of the stepping loop)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline figure too: the single-chain rate (single_replica; --no-single skips it), "
+                    "the CPU baseline (cpu_baseline; --no-cpu), the nonbonded kernel timed in the stepping loop and alone and the roofline block (roofline; "
+                    "--no-kernel-timing).  A plain run leaves them null (cpu_baseline: absent)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: what the last one computed, as DIR/<name>.npy in float64 (64 MB at "
+                    "most): the decision records of every chain, the coordinates and velocities of the mobile atoms of rank 0's chains (dump_outputs)")
     args = ap.parse_args()
 
     # ---- N ranks: either a launcher (torch.distributed.run) already started us as one of them, or we start them ourselves
@@ -452,6 +484,9 @@ def main():
     from blues_amd import simulation
     from blues_amd.replicas import env_rank, init_process_group, replica_seed
     rank, local_rank, world = env_rank()
+    # numpy's global stream seeds every chain's own RandomState (Metropolis draws, velocity seeds at every reset, the set-up's own
+    # start states): seeded per rank, the same arguments give the same inputs from run to run
+    np.random.seed(replica_seed(2718, rank) & 0x7FFFFFFF)
     if args.same_device and args.backend == "nccl" and world > 1:
         sys.stderr.write("bench.py: --same-device needs --backend gloo (RCCL wants one device per rank)\n")
         sys.exit(2)
@@ -491,8 +526,9 @@ def main():
     # ---- configs[1] to the letter: ONE chain on the GPU, a lone engine with a lone engine's layout (its own construction, default tuning)
     single = None
     t_single = time.perf_counter()
-    if rank == 0 and not args.no_single and not args.md_steps:
+    if rank == 0 and args.full and not args.no_single and not args.md_steps:
         clock = {"sync": 0.0, "switch": 0.0, "decide": 0.0}
+        rng_state = np.random.get_state()     # (the lone chain draws from numpy's global stream: put back below, so that the batches' inputs do not depend on --full)
         _, _, lone = build_chains(rank, local_rank, nsteps, args.workload, 1, reciprocal=args.reciprocal)
         st1 = md_states(lone, x0, v0)
         one_switch(None, lone, st1, nsteps, 0, clock)
@@ -510,6 +546,7 @@ def main():
                                "traffic": None, "usec_per_launch": k1_single,
                                "note": "one chain keeps a few of the 256 CUs busy: every kernel of its step is latency-bound (DESIGN.md section 4)"}}
         e1.close()
+        np.random.set_state(rng_state)
     t_single = time.perf_counter() - t_single      # (a measurement, not set-up: taken out of setup_seconds below)
     _stage("single replica measured")
 
@@ -569,7 +606,7 @@ def main():
             ck["_counters"] = drv._ncmc_batch.counters()
     # the nonbonded kernel is timed WHERE IT RUNS: every 4th force launch of the timed switches is bracketed by two HIP events on
     # the batch's stream (blues_batch_kernel_timing); that mean is roofline.usec_per_launch, what rocprofv3 averages for the same loop
-    timing_batch = None if args.no_kernel_timing or not hasattr(drivers[0]._ncmc_batch, "kernel_timing") else drivers[0]._ncmc_batch
+    timing_batch = None if not args.full or args.no_kernel_timing or not hasattr(drivers[0]._ncmc_batch, "kernel_timing") else drivers[0]._ncmc_batch
     if timing_batch is not None:
         timing_batch.kernel_timing(4)
     # the chains' Python objects (contexts, integrators, move engines, state tables: a few thousand per chain) live as long as the
@@ -608,6 +645,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     _stage("timed iterations done")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, recs[-1], drivers, rank)
     st1 = engs[0].stats(); b1 = [d._ncmc_batch.stats() for d in drivers]
     iteration_seconds = [list(ck.get("iterations", [])) for ck in clocks]     # per batch, per timed iteration (with several batches: the turns it waited for included)
     layout_events = [list(ck.get("layout_events", [])) for ck in clocks]       # per batch, per timed iteration
@@ -670,12 +709,12 @@ def main():
         # ---- roofline block of the dominant kernel.  north_star prices it against HBM with 36 B per atom per force evaluation
         # over ALL atoms; the kernel computes forces for the mobile atoms only, so the byte count of what such a pass has to touch
         # is given beside it, and so is the limit that actually binds (VALU issue), each from counters taken on this build.
-        n_i, n_touched, n_pairs = in_range_counts(system)
-        mob_bytes = (24.0 * n_touched + 12.0 * n_i) * R_launch
-        ev = pmc_evidence(args.workload, R_launch)
         est = engs[0].stats()
         roofline = None
         if k1_us is not None:
+          n_i, n_touched, n_pairs = in_range_counts(system)
+          mob_bytes = (24.0 * n_touched + 12.0 * n_i) * R_launch
+          ev = pmc_evidence(args.workload, R_launch)
           achieved = algo / (k1_us * 1e-6) / 1e9
           secs = k1_us * 1e-6
           in_loop = k1_loop is not None and k1_loop["launches"] > 0
@@ -765,7 +804,7 @@ def main():
             "accept_records_last": {"chains": int(last.shape[0]), "accepted": int(last[:, 0].sum()),
                                     "mean_protocol_work_kj": float(np.nanmean(last[:, 3])), "first": last[0].tolist()},
         }
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(system, vel, args.cpu_steps)
         print(json.dumps(out), flush=True)   # (flushed before the chains are torn down at the end of main(): a fault there must not take the line with it; nothing is written after it, on either stream)
     if world > 1:

@@ -6,7 +6,7 @@
 #   water_R1 / water_R16 / sidechain_R64 / reciprocal_R512 / bench_R512 / bench_R2048 / bench_R2048_G4 .json   the other configurations
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/ev_r04; rm -rf $out; mkdir -p $out
-run() { name=$1; shift; python3 bench.py "$@" > $out/$name.log 2>&1; tail -1 $out/$name.log > $out/$name.json; python3 - <<PY
+run() { name=$1; shift; python3 bench.py --full "$@" > $out/$name.log 2>&1; tail -1 $out/$name.log > $out/$name.json; python3 - <<PY
 import json
 try:
     d = json.loads(open("$out/$name.json").read())
@@ -18,7 +18,7 @@ PY
 }
 if [ -z "$OTHERS_ONLY" ]; then   # (OTHERS_ONLY=1: only the other configurations below; the default line and what has to agree with it come from evidence_r04_default.sh)
 run bench_R2048_G2
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats_R2048_G2.csv 2>/dev/null; rm -rf $out/stats
 python3 - <<PY
 import csv

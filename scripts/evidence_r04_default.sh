@@ -8,13 +8,13 @@
 #   bench_R1024.json               one batch of 1024 chains (--groups 1), for comparison
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/ev_r04b; rm -rf $out; mkdir -p $out
-python3 bench.py > $out/bench_R2048_G2.log 2>&1; tail -1 $out/bench_R2048_G2.log > $out/bench_R2048_G2.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_R2048_G2_steps20.log 2>&1; tail -1 $out/bench_R2048_G2_steps20.log > $out/bench_R2048_G2_steps20.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
+python3 bench.py --full > $out/bench_R2048_G2.log 2>&1; tail -1 $out/bench_R2048_G2.log > $out/bench_R2048_G2.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_R2048_G2_steps20.log 2>&1; tail -1 $out/bench_R2048_G2_steps20.log > $out/bench_R2048_G2_steps20.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats_R2048_G2.csv 2>/dev/null; rm -rf $out/stats
 bash scripts/pmc_nb.sh r04 > $out/pmc.log 2>&1; cp gpurun_out/pmc_r04/pmc_nonbonded.json $out/pmc_nonbonded.json; cp $out/pmc_nonbonded.json profiles/r04_pmc_nonbonded.json
-python3 bench.py --no-cpu --no-single > $out/bench_R2048_G2_with_counters.log 2>&1; tail -1 $out/bench_R2048_G2_with_counters.log > $out/bench_R2048_G2_with_counters.json
-python3 bench.py --replicas 1024 --groups 1 --steps 20 --warmup 5 --no-cpu --no-single > $out/bench_R1024.log 2>&1; tail -1 $out/bench_R1024.log > $out/bench_R1024.json
+python3 bench.py --full --no-cpu --no-single > $out/bench_R2048_G2_with_counters.log 2>&1; tail -1 $out/bench_R2048_G2_with_counters.log > $out/bench_R2048_G2_with_counters.json
+python3 bench.py --full --replicas 1024 --groups 1 --steps 20 --warmup 5 --no-cpu --no-single > $out/bench_R1024.log 2>&1; tail -1 $out/bench_R1024.log > $out/bench_R1024.json
 python3 - <<PY
 import json, csv
 for f in ["bench_R2048_G2", "bench_R2048_G2_steps20", "bench_R2048_G2_with_counters", "bench_R1024"]:

@@ -6,7 +6,7 @@
 #   default                 `python bench.py` (chains decorrelated at set-up) and the same with --same-start
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/ev_r05; mkdir -p $out
-run() { name=$1; shift; timeout 1500 python3 bench.py "$@" > $out/$name.log 2>&1; tail -1 $out/$name.log > $out/$name.json; python3 - <<PY
+run() { name=$1; shift; timeout 1500 python3 bench.py --full "$@" > $out/$name.log 2>&1; tail -1 $out/$name.log > $out/$name.json; python3 - <<PY
 import json
 try:
     d = json.loads(open("$out/$name.json").read())

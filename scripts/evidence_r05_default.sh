@@ -8,13 +8,13 @@
 #   bench_default_with_counters.json the default line again once the counters are on disk (roofline.traffic / valu filled in)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/ev_r05d; rm -rf $out; mkdir -p $out
-python3 bench.py > $out/bench_default.log 2>&1; tail -1 $out/bench_default.log > $out/bench_default.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_default_steps20.log 2>&1; tail -1 $out/bench_default_steps20.log > $out/bench_default_steps20.json
-python3 bench.py --same-start --no-cpu --no-single > $out/bench_same_start.log 2>&1; tail -1 $out/bench_same_start.log > $out/bench_same_start.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
+python3 bench.py --full > $out/bench_default.log 2>&1; tail -1 $out/bench_default.log > $out/bench_default.json
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_default_steps20.log 2>&1; tail -1 $out/bench_default_steps20.log > $out/bench_default_steps20.json
+python3 bench.py --full --same-start --no-cpu --no-single > $out/bench_same_start.log 2>&1; tail -1 $out/bench_same_start.log > $out/bench_same_start.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
 cp $out/stats/*/*kernel_stats.csv $out/kernel_stats_default.csv 2>/dev/null; rm -rf $out/stats
 bash scripts/pmc_nb.sh r05 > $out/pmc.log 2>&1; cp gpurun_out/pmc_r05/pmc_nonbonded.json $out/pmc_nonbonded.json; cp $out/pmc_nonbonded.json profiles/r05_pmc_nonbonded.json
-python3 bench.py --no-cpu --no-single > $out/bench_default_with_counters.log 2>&1; tail -1 $out/bench_default_with_counters.log > $out/bench_default_with_counters.json
+python3 bench.py --full --no-cpu --no-single > $out/bench_default_with_counters.log 2>&1; tail -1 $out/bench_default_with_counters.log > $out/bench_default_with_counters.json
 python3 - <<PY
 import json, csv
 for f in ["bench_default", "bench_default_steps20", "bench_same_start", "bench_default_with_counters"]:

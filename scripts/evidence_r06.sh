@@ -10,7 +10,7 @@
 #   step         bare stepping of 1024 chains + its kernel table                                              -> step.txt, kernel_stats_step_R1024.csv
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/ev_r06; mkdir -p $out
-run() { name=$1; shift; timeout 1500 python3 bench.py "$@" > $out/$name.log 2>&1; grep '^{' $out/$name.log | tail -1 > $out/$name.json; python3 - <<PY
+run() { name=$1; shift; timeout 1500 python3 bench.py --full "$@" > $out/$name.log 2>&1; grep '^{' $out/$name.log | tail -1 > $out/$name.json; python3 - <<PY
 import json
 try:
     d = json.loads(open("$out/$name.json").read())
@@ -26,7 +26,7 @@ what="${@:-default stats pmc counters solute}"
 for w in $what; do case $w in
   default) run bench_default_steps20 --gpus 1 --steps 20 --warmup 5 ;;
   stats)
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-single > $out/stats.log 2>&1
     cp $out/stats/*/*kernel_stats.csv $out/kernel_stats_default.csv 2>/dev/null; rm -rf $out/stats
     python3 - <<PY
 import csv, os

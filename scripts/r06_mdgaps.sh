@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=${1:-64}
 out=gpurun_out/r06/mdgaps_$R; rm -rf $out; mkdir -p $out
-timeout 900 rocprofv3 --kernel-trace --output-format csv -d $out/tr -- python3 bench.py --md-steps 300 --replicas $R --groups 1 --steps 1 --warmup 1 --no-cpu --no-single > $out/log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv -d $out/tr -- python3 bench.py --full --md-steps 300 --replicas $R --groups 1 --steps 1 --warmup 1 --no-cpu --no-single > $out/log 2>&1
 python3 - <<PY
 import csv, glob, collections
 f = glob.glob("$out/tr/*/*kernel_trace.csv")[0]

@@ -21,6 +21,7 @@ step 20 AFTER the move and at step 40, so that a mixed-precision engine can be t
 Oracle (fp64 CPU restatement) outputs, NOT reference outputs: OpenMM cannot run here (oracle/blues_oracle.h).
 """
 import copy
+import glob
 import os
 import sys
 import time
@@ -83,9 +84,9 @@ def variant(name):
 def main():
     out = {"nsteps": NSTEPS, "move_step": MOVE_STEP, "dt": 0.004, "temperature": 300.0, "lambdas": np.array(LAMBDAS)}
     path = os.path.join(ROOT, "tests", "golden", "s23k_variant_vectors.npz")
-    only = sys.argv[1:]       # (variants to (re)generate; the others are kept from the committed file)
+    only = sys.argv[1:]       # (variants to (re)generate; the others are kept from the committed files)
     if only and os.path.exists(path):
-        out.update({k: v for k, v in np.load(path).items() if not any(k.startswith(n + "_") for n in only)})
+        out.update({k: v for k, v in load(path).items() if not any(k.startswith(n + "_") for n in only)})
     for name in (only or ("water", "sidechain", "solute")):
         s, v, move = variant(name)
         mob = np.nonzero(s.mass > 0)[0]
@@ -115,8 +116,31 @@ def main():
         out[p + "work_trace"] = np.array(work); out[p + "work_before_move_step"] = wm
         out[p + "x_after_move"] = xm.astype(np.float64); out[p + "v_at_move"] = vm.astype(np.float64)
         out[p + "x_end"] = o.get_positions()[mob]
-    np.savez_compressed(path, **out)
+    save(path, out)
+
+
+SPLIT_BYTES = 256 * 1024     # arrays larger than this go to files of their own: no committed file may exceed 1 MiB
+
+
+def save(path, out):
+    """`path` holds the small arrays; every large one goes to <path without .npz>.<key>.npz."""
+    stem = path[:-len(".npz")]
+    for f in glob.glob(stem + ".*.npz"):
+        os.remove(f)
+    big = {k for k, v in out.items() if np.asarray(v).nbytes > SPLIT_BYTES}
+    np.savez_compressed(path, **{k: v for k, v in out.items() if k not in big})
     print("wrote", path, os.path.getsize(path), "bytes")
+    for k in sorted(big):
+        np.savez_compressed("%s.%s.npz" % (stem, k), **{k: out[k]})
+        print("wrote", "%s.%s.npz" % (stem, k), os.path.getsize("%s.%s.npz" % (stem, k)), "bytes")
+
+
+def load(path):
+    """Every array of `path` and of the files save() split off beside it."""
+    out = dict(np.load(path))
+    for f in sorted(glob.glob(path[:-len(".npz")] + ".*.npz")):
+        out.update(np.load(f))
+    return out
 
 
 if __name__ == "__main__":

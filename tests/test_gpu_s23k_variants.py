@@ -1,5 +1,5 @@
 """GPU suite: the S23k system VARIANTS bench.py runs beside the headline configuration, at full size, against committed oracle
-vectors (tests/golden/s23k_variant_vectors.npz; generator: tests/golden/make_s23k_variant_vectors.py):
+vectors (tests/golden/s23k_variant_vectors*.npz; generator: tests/golden/make_s23k_variant_vectors.py):
 
   water     -- BASELINE.json configs[3]: nothing frozen (23,400 mobile atoms, 366 i-tiles), 40 position restraints, the first water
                alchemical (reference examples/example_water.py, blues/moves.py:846-1083);
@@ -14,6 +14,7 @@ Bar (north_star): energies, forces, protocol work within 1e-5 relative of the fp
 The 40-step work trace is compared teacher-forced at the move step (step 20), lone and in replica batches.
 """
 import copy
+import glob
 import os
 
 import numpy as np
@@ -38,7 +39,11 @@ def Engine():
 
 @pytest.fixture(scope="module")
 def gold():
-    return dict(np.load(GOLD))
+    # the large arrays sit in files of their own beside GOLD (s23k_variant_vectors.<key>.npz: make_s23k_variant_vectors.save)
+    out = dict(np.load(GOLD))
+    for f in sorted(glob.glob(GOLD[:-len(".npz")] + ".*.npz")):
+        out.update(np.load(f))
+    return out
 
 
 def _variant(name):

@@ -10,6 +10,7 @@ import pytest
 from blues_amd import _abi, amber, build, integrators, lepton, moves, simulation, systems, unit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def _have_hipcc():
@@ -118,13 +119,13 @@ def test_unit_shim():
         unit.Quantity(1.0, "kelvin").value_in_unit("nanometer")
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/blues/tests/data/TOL-parm.prmtop"), reason="reference checkout not present")
 def test_amber_reader_on_reference_fixture(known_answers, tol_box):
-    prm = amber.read_prmtop("/root/reference/blues/tests/data/TOL-parm.prmtop")
+    # the reference's own test inputs (blues/tests/data/TOL-parm.*), stored under tests/golden/
+    prm = amber.read_prmtop(os.path.join(GOLDEN, "TOL-parm.prmtop"))
     p = known_answers["tol_parm_pointers"]
     assert int(prm["POINTERS"][0]) == p["NATOM"] and int(prm["POINTERS"][1]) == p["NTYPES"]
     assert int(prm["POINTERS"][2]) == p["NBONH"] and int(prm["POINTERS"][10]) == p["NNB"] and int(prm["POINTERS"][11]) == p["NRES"]
-    pos, vel, box = amber.read_inpcrd("/root/reference/blues/tests/data/TOL-parm.inpcrd")
+    pos, vel, box = amber.read_inpcrd(os.path.join(GOLDEN, "TOL-parm.inpcrd"))
     assert pos.shape == (975, 3) and np.allclose(box, 2.1786)
     s = amber.system_from_amber(prm, pos, box, hydrogen_mass=3.024, alchemical_atoms=range(15))
     ref, _ = tol_box
