@@ -13,7 +13,7 @@ import re
 
 import numpy as np
 
-from ._abi import NB_PME, NB_PME_DIRECT, SystemData
+from ._abi import NB_NOCUTOFF, NB_PME, NB_PME_DIRECT, SystemData
 
 AMBER_CHARGE = 18.2223
 KCAL = 4.184
@@ -127,7 +127,7 @@ def ewald_alpha(cutoff, tolerance):
 
 def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.005, constraints="HBonds",
                       rigid_water=True, hydrogen_mass=None, remove_cm_motion=True, alchemical_atoms=(),
-                      tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True):
+                      tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME"):
     """Amber topology -> SystemData, following structure.createSystem's kwargs
     (reference examples/rotmove_cuda.yml:19-27: PME, 10 A cutoff, HBonds,
     rigidWater, removeCMMotion, hydrogenMass 3.024, ewaldErrorTolerance 0.005).
@@ -135,7 +135,16 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     (they contribute zero at the constrained geometry).
     reciprocal_space=True is nonbondedMethod=PME in full (mesh of OpenMM's Reference platform for the tolerance, self term,
     excluded-pair corrections, dispersion correction); False keeps the direct-space sum only and says so in the log --
-    forces on the water then differ from the reference's, only the protocol work (lambda-dependent pairs) does not."""
+    forces on the water then differ from the reference's, only the protocol work (lambda-dependent pairs) does not.
+    nonbonded_method="NoCutoff" (vacuum, reference blues/tests/test_sidechain.py:42): every pair counts, no cutoff, no periodicity,
+    no mesh and no dispersion correction; `box` may be None (the box is then stored as zeros and has no effect)."""
+    if nonbonded_method not in ("PME", "NoCutoff"):
+        raise ValueError("nonbonded_method must be 'PME' or 'NoCutoff', got %r" % (nonbonded_method,))
+    no_cutoff = nonbonded_method == "NoCutoff"
+    if box is None:
+        if not no_cutoff:
+            raise ValueError("a periodic System (nonbonded_method='PME') needs a box")
+        box = np.zeros(3)
     p = prm["POINTERS"]
     natom, ntypes = int(p[0]), int(p[1])
     charge = prm["CHARGE"] / AMBER_CHARGE
@@ -253,7 +262,9 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     exc_pairs = sorted(exc.keys())
 
     alpha = ewald_alpha(cutoff, ewald_error_tolerance)
-    if reciprocal_space:
+    if no_cutoff:
+        method, grid, alpha, dispersion_correction = NB_NOCUTOFF, (0, 0, 0), 0.0, False
+    elif reciprocal_space:
         from .systems import pme_grid_for
         method, grid = NB_PME, pme_grid_for(box, alpha, cutoff, ewald_error_tolerance)
     else:

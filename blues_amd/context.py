@@ -265,6 +265,8 @@ class Simulation(object):
     describeNextReport(sim) -> (steps, pos, vel, frc, ene) / report(sim, state)."""
 
     def __init__(self, topology, system, integrator, platform=None, platformProperties=None, device=0, precision="mixed", replica=0):
+        if getattr(system, "barostat", None) and getattr(system, "nonbonded_method", None) == 0:   # (as OpenMM: a barostat needs a periodic System)
+            raise ValueError("a MonteCarloBarostat cannot be used with a non-periodic System (nonbondedMethod=NoCutoff)")
         props = dict(platformProperties or {})
         device = int(props.get("DeviceIndex", device))
         precision = props.get("Precision", precision)

@@ -37,6 +37,7 @@
 #include "kernels_nb.h"
 #include "kernels_pme.h"
 #include "kernels_batch.h"
+#include "kernels_nocutoff.h"
 
 static thread_local std::string g_create_error;
 // set-up cost accounting (diagnostic, blues_debug_setup_seconds): [0] blues_engine_create, [1] sort_and_tile, [2] its device uploads,
@@ -279,7 +280,8 @@ struct BluesEngine {
     int seg_len = 64, waves_tile = 4, wpb = 4, npart = 1;  // K1 decomposition
     bool fuse_forces = false, fast_step = true, fuse_big = false;  // fuse_big: measured slower (the alchemical role's 140 VGPRs and 36 KB LDS cap the occupancy of the nonbonded role)
     int k1_iw = 64;  // i-atoms per wave in the nonbonded kernel: 64 = classic tile kernel, 8/16 = sub-tile throughput kernel
-    int k1_mode = 0;  // 0: tile kernel (lane = i-atom), 1: sub-tile kernel, 2: per-atom Verlet lists + LDS tile image (nonbonded_atom_body), 3: fragment lists (kernels_frag.h)
+    int k1_mode = 0;  // 0: tile kernel (lane = i-atom), 1: sub-tile kernel, 2: per-atom Verlet lists + LDS tile image (nonbonded_atom_body), 3: fragment lists (kernels_frag.h), 4: all pairs of a NoCutoff System (kernels_nocutoff.h)
+    DBuf<double4> d_ncpar; int nc_blocks_f = 0, nc_blocks_e = 0;   // NoCutoff: per-atom parameters, blocks of the force / energy launches (nocut_layout)
     // fragment lists (every environment atom mobile): the static cut of the environment into fragments of <= 3 atoms
     // (build_fragments), the layout of the current sort, the lists
     std::vector<std::array<int, 3>> frag_atoms; std::vector<int> frag_cnt, frag_of_atom, frag_pos_of_atom; bool frag_ok = false, frag_built = false;   // (bonds and constraints: what holds a molecule together)
@@ -396,6 +398,7 @@ struct BluesBatch {
     struct EvPair { hipEvent_t a = nullptr, b = nullptr; bool busy = false; };
     std::vector<const BluesEngine*> congr_lead; std::vector<uint64_t> congr_le, congr_me;   // congruence already established (batch_do_steps)
     bool defer_work = false; std::vector<DevAccum*> h_wacc; std::vector<double> h_wdelta; DBuf<DevAccum*> d_wacc; DBuf<double> d_wdelta;   // add_work of all members in one launch
+    DBuf<NcArgs> d_nc;   // NoCutoff members: the records of the all-pairs kernel (batch_refresh_args)
     std::vector<EvPair> k1t_pairs; int k1t_every = 0; int64_t k1t_seen = 0, k1t_n = 0; double k1t_sum_us = 0.0, k1t_max_us = 0.0;
     int R() const { return (int)eng.size(); }
 };
@@ -425,9 +428,13 @@ static inline bool batch_lead(const BluesEngine* h) { return h->batch && h->batc
 static inline int* batch_req_ptr(const BluesEngine* h) { return h->batch && h->batch->sync_lists ? h->batch->d_req.p : nullptr; }
 template <typename R> static const RepNb<R>* batch_reps_nb(const BluesBatch* b) { if constexpr (sizeof(R) == 4) return b->d_nb_f.p; else return b->d_nb_d.p; }
 
+static inline bool nocut(const BluesEngine* h) { return h->nb_method == BLUES_NB_NOCUTOFF; }
+// NoCutoff: a box that does not wrap (L = invL = 0: min_image_d returns the difference itself), whatever box is stored -- zero included
 static Box3 make_box(const BluesEngine* h) {
-    Box3 b; for (int k = 0; k < 3; k++) { b.L[k] = h->box[k]; b.invL[k] = 1.0 / h->box[k]; } return b;
+    Box3 b; for (int k = 0; k < 3; k++) { b.L[k] = nocut(h) ? 0.0 : h->box[k]; b.invL[k] = nocut(h) ? 0.0 : 1.0 / h->box[k]; } return b;
 }
+// the lattice translation that brings a cluster atom next to the cluster's first atom (none without periodicity)
+static inline double lattice_shift(const BluesEngine* h, int k, double d) { return nocut(h) ? 0.0 : h->box[k] * std::nearbyint(d / h->box[k]); }
 // List margins.  A pair's separation changes by at most the sum of its atoms' displacements since the build, and a rebuild
 // is requested as soon as ONE mobile atom has moved `trig`: a frozen candidate therefore needs a margin of trig, a mobile one
 // 2 trig.  Where nearly everything is frozen (freeze_radius, reference blues/simulation.py:394-480) the few mobile
@@ -774,7 +781,102 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
 
 // ------------------------------------------------------------------ spatial sort + tile image (host, at set_positions)
 static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
+// NoCutoff (k1_mode 4): the one layout of the engine's life, made at creation from the topology alone -- no spatial sort (the
+// "sorted" order is the caller's), no tiles to re-sort, no lists.  The i-slots are the mobile non-alchemical atoms in caller order;
+// the alchemical kernel's j-list is every environment atom, static; the partial slabs are shaped for k_finalize as the other modes
+// leave them (one nonbonded slab), so the sums, the step kernels and the batched records are the periodic path's.
+static int nocut_layout(BluesEngine* h) {
+    const int n = h->n;
+    h->k1_mode = 4; h->S = 1; h->acap = 0; h->k1_iw = 64; h->seg_len = 64; h->waves_tile = 1; h->npart = 1; h->wpb = 4;
+    h->fuse_forces = false; h->fuse_big = false; h->k2_dense = false; h->k2_f32 = false; h->prune_on = false; h->use_graph = false;
+    h->skin = h->skin_m = h->trig = 1e30;   // (the step kernels' displacement check never asks for a list)
+    h->h_sorted_of_orig.resize(n); h->h_orig_of_sorted.resize(n);
+    for (int i = 0; i < n; i++) { h->h_sorted_of_orig[i] = i; h->h_orig_of_sorted[i] = i; }
+    std::vector<int> tile_atoms, islot(n, -1), env;
+    for (int i = 0; i < n; i++) {
+        if (h->T->alch_local[i] >= 0) continue;
+        env.push_back(i);
+        if (h->T->mass[i] != 0.0) { islot[i] = (int)tile_atoms.size(); tile_atoms.push_back(i); }
+    }
+    h->n_itiles = ((int)tile_atoms.size() + 63) / 64;
+    h->n_islots = std::max(1, h->n_itiles) * 64;
+    tile_atoms.resize(h->n_islots, -1);
+    h->n_lists = 0; h->n_tiles = h->alch.empty() ? 0 : 1;
+    h->jcap = std::max(64, (((int)env.size() + 63) / 64) * 64);
+    h->pool_cap = MASK_QUOTA; h->hint_count = h->jcap;
+    h->PA = 1; while (h->PA < (int)h->alch.size()) h->PA <<= 1;
+    h->k2_jiter = std::min(4, h->PA);   // (a function of the topology only: a chain's sums are ordered alike alone and in a batch)
+    h->k2_nblocks_env = k2_env_blocks((int)env.size(), h->PA, h->k2_jiter);
+    h->nc_blocks_f = (int)(((size_t)h->n_islots + NC_THREADS - 1) / NC_THREADS);
+    h->nc_blocks_e = (n + NC_THREADS - 1) / NC_THREADS;
+    // exclusion rows in caller order, self included, ascending and without repeats (the all-pairs kernel walks them with a cursor)
+    std::vector<int> ex_start(n + 1, 0), ex_idx;
+    for (int i = 0; i < n; i++) {
+        std::vector<int> row(h->T->excl[i]); row.push_back(i);
+        std::sort(row.begin(), row.end()); row.erase(std::unique(row.begin(), row.end()), row.end());
+        ex_idx.insert(ex_idx.end(), row.begin(), row.end());
+        ex_start[i + 1] = (int)ex_idx.size();
+    }
+    const double sq = std::sqrt(ONE_4PI_EPS0);
+    std::vector<double4> par(n);
+    for (int i = 0; i < n; i++) {
+        const bool al = h->T->alch_local[i] >= 0;
+        par[i] = al ? make_double4(0.0, 0.0, 0.0, 1.0) : make_double4(h->T->charge[i] * sq, 0.5 * h->T->sigma[i], 2.0 * std::sqrt(h->T->eps[i]), 0.0);
+    }
+    try {
+        h->d_ncpar.upload(par);
+        h->d_sorted_of_orig.upload(h->h_sorted_of_orig); h->d_orig_of_sorted.upload(h->h_orig_of_sorted);
+        h->d_tile_atoms.upload(tile_atoms); h->d_islot.upload(islot);
+        h->d_ex_start.upload(ex_start); h->d_ex_idx.upload(ex_idx);
+        // (the step kernels refresh a fixed-point image of whatever box they are given: a buffer nobody reads here)
+        if (h->precision == 0) h->d_img_f.alloc(n); else h->d_img_d.alloc(n);
+        { std::vector<int> cs(h->clusters.size() * 4, 0);
+          for (size_t c = 0; c < h->clusters.size(); c++) for (int a = 0; a < 4; a++) if (h->clusters[c].atoms[a] >= 0) cs[c * 4 + a] = h->clusters[c].atoms[a];
+          h->d_cl_sorted.upload(cs);
+          for (size_t c = 0; c < h->clusters.size(); c++) for (int a = 0; a < 4; a++) {
+              const int at = h->clusters[c].atoms[a];
+              h->h_recs[c].sorted[a] = cs[c * 4 + a]; h->h_recs[c].islot[a] = at >= 0 ? islot[at] : -1;
+              const int row = at >= 0 && !h->h_row_of_orig.empty() ? h->h_row_of_orig[at] : -1;
+              h->h_recs[c].e0[a] = row >= 0 ? h->h_row_start[row] : 0; h->h_recs[c].e1[a] = row >= 0 ? h->h_row_start[row + 1] : 0;
+          }
+          h->d_recs.upload(h->h_recs); }
+        { std::vector<AlchJRec> jr(env.size());
+          for (size_t q = 0; q < env.size(); q++) { const int j = env[q]; jr[q].jo = j; jr[q].jsrt = j | (h->T->mass[j] != 0.0 ? (1 << 30) : 0); jr[q].sig = h->T->sigma[j]; jr[q].eps = std::sqrt(h->T->eps[j]); jr[q].q = h->T->charge[j]; }
+          if (jr.empty()) jr.resize(1);
+          h->d_jrec.upload(jr);
+          std::vector<int> cnt(1, (int)env.size()); h->d_jcount.upload(cnt); }
+        { std::vector<AlchARec> ar(h->alch.size());
+          for (size_t a2 = 0; a2 < h->alch.size(); a2++) { AlchARec& r = ar[a2]; const int ao = h->alch[a2]; r.ao = ao; r.asrt = ao; r.pad = 0; r.sig = h->T->sigma[ao]; r.eps = std::sqrt(h->T->eps[ao]); r.q = h->T->charge[ao];
+            r.has_env_excl = 0; for (int p2 : h->T->excl[ao]) if (h->T->alch_local[p2] < 0) r.has_env_excl = 1; }
+          h->d_arec.upload(ar); }
+        h->d_fpart.alloc((size_t)3 * h->n_islots);
+        h->d_epart_nb.alloc((size_t)2 * std::max(h->nc_blocks_e, h->nc_blocks_f));
+        { std::vector<int> ooi(h->n_islots, -1); for (int o = 0; o < n; o++) if (islot[o] >= 0) ooi[islot[o]] = o; h->d_orig_of_islot.upload(ooi);
+          std::vector<FinRec> fr(h->n_islots + 64);
+          auto fill = [&](FinRec& r, int atom) {
+              r.atom = atom; r.sorted = 0; r.e0 = r.e1 = 0;
+              if (atom >= 0) { r.sorted = atom; const int row = h->h_row_of_orig[atom]; if (row >= 0) { r.e0 = h->h_row_start[row]; r.e1 = h->h_row_start[row + 1]; } }
+          };
+          for (int q = 0; q < h->n_islots; q++) fill(fr[q], ooi[q]);
+          for (int a = 0; a < 64; a++) fill(fr[h->n_islots + a], a < (int)h->alch.size() ? h->alch[a] : -1);
+          h->d_finrecs.upload(fr); }
+        h->d_fJ.alloc((size_t)9 * n);
+        h->d_self_part.alloc((size_t)(h->k2_nblocks_env + 1) * 9 * 64); h->d_e_part.alloc((size_t)(h->k2_nblocks_env + 1) * K2_NP); h->d_mom_part.alloc((size_t)(h->n_islots / 64 + 2) * 6);
+    } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+    // no frozen-frozen constant: the all-pairs energy kernel has every pair
+    h->e_frozen[0] = h->e_frozen[1] = 0.0; h->e_frozen_valid = true;
+    h->sorted_ok = true; h->lists_forced = false; h->pass_valid = false; h->graph_valid = false;
+    h->layout_R = h->batch_R;
+    h->args_epoch++;
+    return 0;
+}
+
 static int sort_and_tile(BluesEngine* h) {
+    if (nocut(h)) {   // (the layout made at creation holds for the engine's life: nothing to sort, whatever the caller's reason)
+        std::vector<double>().swap(h->hx);
+        h->sorted_ok = true; h->layout_R = h->batch_R; h->e_frozen_valid = true;
+        return 0;
+    }
     SetupTimer tm_all(1);
     const int n = h->n;
     if (h->hx.size() != (size_t)3 * n) {   // (the positions this layout is made from: normally filled by the caller; the copy is dropped when the layout is done)
@@ -1323,6 +1425,7 @@ static FragArgs make_frag_args(BluesEngine* h) {
 // phase 0: the whole rebuild; 1: the group lists only (k_build_lists); 2: the atoms' own lists only (k_build_atom_lists);
 // a batch's leader also: 3: the work list only (k_gather_stale_b); 4: the group lists without the work list (1 = 3 then 4)
 template <typename R> static int launch_lists(BluesEngine* h, int force, int phase = 0) {
+    if (h->k1_mode == 4) return 0;   // (NoCutoff: every pair, no lists)
     if (h->tune.force_lists) force = 1;   // development: every launch rebuilds every list
     const ListArgs a = make_list_args(h);
     const typename Img<R>::Atom* img;
@@ -1436,7 +1539,25 @@ template <bool ENERGY> static void launch_nb_sub(BluesEngine* h, const NbArgs<fl
     else hipLaunchKernelGGL((k_nonbonded_sub<ENERGY, 32>), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
 }
 
+static NcArgs make_nc_args(BluesEngine* h) {
+    NcArgs a; memset(&a, 0, sizeof a);
+    a.active = 1; a.n = h->n; a.n_islots = h->n_islots;
+    for (int k = 0; k < 3; k++) a.x[k] = h->d_x[k].p;
+    a.par = h->d_ncpar.p; a.tile_atoms = h->d_tile_atoms.p; a.ex_start = h->d_ex_start.p; a.ex_idx = h->d_ex_idx.p;
+    a.fpart = h->d_fpart.p; a.epart = h->d_epart_nb.p;
+    return a;
+}
+// NoCutoff: the all-pairs kernel (kernels_nocutoff.h); a batch's leader launches it once for every member (gridDim.y)
+template <typename R, bool ENERGY> static int launch_nocut(BluesEngine* h) {
+    const int nb = ENERGY ? h->nc_blocks_e : h->nc_blocks_f;
+    if (batch_lead(h)) hipLaunchKernelGGL((k_nocutoff_b<R, ENERGY>), dim3(nb, h->batch->R()), dim3(NC_THREADS), 0, h->cur, h->batch->d_nc.p);
+    else if (!batch_dry(h)) hipLaunchKernelGGL((k_nocutoff<R, ENERGY>), dim3(nb), dim3(NC_THREADS), 0, h->cur, make_nc_args(h));
+    h->st_launches++;
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
 template <typename R, bool ENERGY> static int launch_nonbonded(BluesEngine* h) {
+    if (h->k1_mode == 4) return launch_nocut<R, ENERGY>(h);
     NbArgs<R> a = make_nb_args<R>(h);
     if constexpr (sizeof(R) == 4) {
         if (h->k1_mode == 3) {
@@ -1585,7 +1706,7 @@ static AlchArgs make_alch_args(BluesEngine* h, const double ls[3], const double 
     for (int k = 0; k < 3; k++) A.x[k] = h->d_x[k].p;
     A.charge = h->d_charge.p; A.sigma = h->d_sigma.p; A.eps = h->d_eps.p; A.ex_start = h->d_ex_start.p; A.ex_idx = h->d_ex_idx.p;
     A.exc_start = h->d_exc_start.p; A.exc_partner = h->d_exc_partner.p; A.exc_owner = h->d_exc_owner.p; A.exc_is_env = h->d_exc_is_env.p; A.exc_params = h->d_exc_params.p;
-    A.box = make_box(h); A.rc2 = h->cutoff * h->cutoff; A.alpha = h->alpha; A.sc_alpha = h->sc_alpha;
+    A.box = make_box(h); A.rc2 = nocut(h) ? 1e300 : h->cutoff * h->cutoff; A.alpha = h->alpha; A.sc_alpha = h->sc_alpha;
     A.pme = h->nb_method == BLUES_NB_PME_DIRECT; A.annih_elec = h->annih_elec; A.annih_ster = h->annih_ster; A.slot_mask = slot_mask; A.check_env_excl = h->check_env_excl;
     for (int s = 0; s < 3; s++) { A.ls[s] = ls[s]; A.le[s] = le[s]; }
     A.fJ = h->d_fJ.p; A.self_part = h->d_self_part.p; A.e_part = h->d_e_part.p; A.ctrl = h->ctrl_arg;
@@ -1656,7 +1777,7 @@ static int launch_finalize(BluesEngine* h, const double le[3], int slot_mask = 7
 // program are served by this pass (slots 0 and 2).  What else needs the summed forces resolves the pending sums first.
 // (npart == 1: the per-atom-list kernel's single slab; a lone chain's tile kernel leaves dozens of partial slabs, and four atoms per
 // thread summing them one after the other took longer than k_finalize's thread per atom: 77 against 52 us per step)
-static bool fin_fusable(const BluesEngine* h) { return h->fast_step && h->int_blocks == 1 && (h->int_threads == 256 || (h->int_threads == 128 && h->clusters_packed)) && h->npart == 1 && h->n_entries <= STEP_FENT_LDS && h->tune.fuse_finalize != 0 && !h->ctrl_arg; }   // (one slab, the bonded entries fit the step kernel's LDS: step_default_body<CM, true>)
+static bool fin_fusable(const BluesEngine* h) { return !nocut(h) && h->fast_step && h->int_blocks == 1 && (h->int_threads == 256 || (h->int_threads == 128 && h->clusters_packed)) && h->npart == 1 && h->n_entries <= STEP_FENT_LDS && h->tune.fuse_finalize != 0 && !h->ctrl_arg; }   // (one slab, the bonded entries fit the step kernel's LDS: step_default_body<CM, true>)
 static int launch_finalize_deferred(BluesEngine* h, const double le[3], int slot_mask) {
     if (!fin_fusable(h) || (slot_mask & 5) != 5) { h->fin_pending = false; return launch_finalize(h, le, slot_mask); }
     h->fin_pending = true; h->fin_mask = slot_mask;
@@ -1872,7 +1993,7 @@ static int resolve_xfer(BluesEngine* h) {
     h->xfer_pending = false;
     HIP_OK(h, hipStreamSynchronize(h->xfer_stream));
     const unsigned* out = h->xfer_src ? h->xfer_src : h->h_xfer;
-    if (out[0]) { h->e_frozen_valid = false; h->pme_static_valid = false; }
+    if (out[0] && !nocut(h)) { h->e_frozen_valid = false; h->pme_static_valid = false; }   // (NoCutoff: no frozen-frozen constant -- the all-pairs energy kernel has those pairs)
     float worst; memcpy(&worst, &out[1], sizeof worst);
     // tiles are formed from the mobile non-alchemical atoms.  A few wandering i-atoms only stretch their tile's bounding
     // box, and the device notices when that starts to cost (resort_hint); the host re-sorts when an i-atom is far out
@@ -1887,7 +2008,7 @@ static int resolve_xfer(BluesEngine* h) {
     // iteration with the atoms a few tenths of a nm from the sort -- re-sorting for those cost 2 x 5 ms per chain and iteration
     const float far = (h->k1_mode == 2 && h->xfer_foreign) ? 0.09f : 1.0f;   // (squared displacement: 0.3 nm / 1 nm)
     h->xfer_foreign = false;
-    if (h->sorted_ok && h->k1_mode != 3 && (worst > far || (int)out[2] > h->n / 10)) h->sorted_ok = false;   // (the layout that follows fetches the positions itself: sort_and_tile)
+    if (h->sorted_ok && h->k1_mode != 3 && h->k1_mode != 4 && (worst > far || (int)out[2] > h->n / 10)) h->sorted_ok = false;   // (the layout that follows fetches the positions itself: sort_and_tile)
     return 0;
 }
 
@@ -2215,6 +2336,7 @@ static EnergyShape energy_shape(const BluesEngine* h) {
     g.nw = (h->k1_mode == 2 ? h->n_lists : h->n_itiles) * h->npart * subs;
     g.off_frozen = (size_t)std::max(1, h->n_itiles) * h->npart * 2 * subs;
     if (h->k1_mode == 3) { g.nw = h->frag_nwg; g.off_frozen = (size_t)2 * h->frag_nwg; }   // one (LJ, Coulomb) pair per workgroup of the fragment kernel
+    if (h->k1_mode == 4) { g.nw = h->nc_blocks_e; g.off_frozen = (size_t)2 * h->nc_blocks_e; }   // one (LJ, Coulomb) pair per block of the all-pairs kernel (it has every pair: no frozen-frozen constant)
     int total_terms = 0; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     g.nbb = (total_terms + 255) / 256; g.nfb = (h->n + FROZEN_TILE - 1) / FROZEN_TILE;
     return g;
@@ -2280,6 +2402,7 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
     h->st_energy_evals++;
     if (energy_launch(h)) return 1;
     const EnergyShape g = energy_shape(h);
+    if (nocut(h)) { h->e_frozen[0] = h->e_frozen[1] = 0.0; h->e_frozen_valid = true; }   // (its partial slab has no room for the frozen kernels' output, nor any use for it)
     if (!h->e_frozen_valid) {
         double* ep = h->d_epart_nb.p + g.off_frozen;
         if (h->precision == 0) {
@@ -2628,7 +2751,7 @@ static int do_steps(BluesEngine* h, int nsteps) {
             if (adv < 0) return 1;
             if (adv > 0) { s += adv - 1; continue; }
         }
-        if (h->h_step > 0 && h->h_step % RESORT_POLL == 0 && poll_resort(h)) return 1;
+        if (!nocut(h) && h->h_step > 0 && h->h_step % RESORT_POLL == 0 && poll_resort(h)) return 1;   // (NoCutoff: no lists, nothing to poll)
         if (step_head(h)) return 1;
         if (step_body(h)) return 1;
     }
@@ -2682,6 +2805,7 @@ static BatchSig batch_sig(const BluesEngine* h) {
 
 // static shape of a member: launch geometry and protocol.  All members must agree.
 static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const char** why) {
+    if (nocut(a) != nocut(b)) { *why = "nonbonded method (a NoCutoff engine and a periodic one cannot share a batch)"; return false; }
 #define BC(f) if (a->f != b->f) { *why = #f; return false; }
     BC(device) BC(n) BC(precision) BC(nsteps) BC(nprop) BC(n_lambda) BC(split) BC(remove_cm) BC(dt) BC(gamma) BC(kT) BC(tol) BC(prop_min) BC(prop_max)
     BC(n_itiles) BC(n_tiles) BC(jcap) BC(n_islots) BC(pool_cap) BC(PA) BC(k2_nblocks_env) BC(k2_jiter) BC(seg_len) BC(waves_tile) BC(wpb) BC(npart)
@@ -2719,6 +2843,8 @@ static int batch_refresh_args(BluesBatch* B) {
     if (!dirty) return 0;
     const double one[3] = {1.0, 1.0, 1.0};
     std::vector<RepCore> core(B->R()); std::vector<RepNb<float>> nf; std::vector<RepNb<double>> nd;
+    const bool no_cutoff = nocut(B->eng[0]);
+    std::vector<NcArgs> nc(no_cutoff ? B->R() : 0);
     const bool single = B->eng[0]->precision == 0;
     if (single) nf.resize(B->R()); else nd.resize(B->R());
     for (int r = 0; r < B->R(); r++) {
@@ -2727,6 +2853,7 @@ static int batch_refresh_args(BluesBatch* B) {
         core[r].active = B->rec_active[r];
         B->rec_delta[r] = h->h_draw - lead->h_draw; core[r].draw_delta = B->rec_delta[r];
         if (single) nf[r].active = B->rec_active[r]; else nd[r].active = B->rec_active[r];
+        if (no_cutoff) { nc[r] = make_nc_args(h); nc[r].active = B->rec_active[r] && h->sorted_ok; }
         if (!h->sorted_ok) { core[r].active = 0; if (single) nf[r].active = 0; else nd[r].active = 0; continue; }  // buffers not laid out (its sort failed): never touched
         core[r].al = make_alch_args(h, one, one, 7); core[r].bo = make_bonded_args(h); core[r].fin = make_fin_args(h, one); core[r].in = make_int_args(h);
         core[r].in.work_trace = h->d_trace.p;  // the launch decides whether it is written (IntDyn.tracing)
@@ -2737,7 +2864,7 @@ static int batch_refresh_args(BluesBatch* B) {
     }
     // the records may be in use by launches still in flight
     if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-    try { B->d_core.upload(core); if (single) B->d_nb_f.upload(nf); else B->d_nb_d.upload(nd); } catch (std::string& e) { B->err = e; return 1; }
+    try { B->d_core.upload(core); if (single) B->d_nb_f.upload(nf); else B->d_nb_d.upload(nd); if (no_cutoff) B->d_nc.upload(nc); } catch (std::string& e) { B->err = e; return 1; }
     return 0;
 }
 
@@ -2778,7 +2905,7 @@ static int batch_prefetch(BluesBatch* B, int what) {
             // positions -- in one launch over a work list; member by member this was a full lone energy evaluation with its host
             // synchronisations each, 0.7 s per 1024 chains and iteration (half of the NCMC leg of a real run)
             std::vector<int> lack;
-            for (int r = 0; r < R; r++) if (live[r] && !B->eng[r]->e_frozen_valid) lack.push_back(r);
+            for (int r = 0; r < R; r++) if (live[r] && !B->eng[r]->e_frozen_valid && !nocut(B->eng[r])) lack.push_back(r);
             bool together = lack.size() > 1;
             for (size_t q = 0; q < lack.size() && together; q++) { const char* why = ""; together = batch_congruent_cached(B, lack[q], lead, &why) && B->eng[lack[q]]->prog.n == 0; }
             if (together) {
@@ -2983,7 +3110,7 @@ static int batch_do_steps(BluesBatch* B, int n_steps, bool tracing, int* status)
         // one gathered read-back tells which members (if any) need the per-member treatment
         {
             bool due = false;
-            for (int r = 0; r < R; r++) due |= !B->failed[r] && B->eng[r]->h_step > 0 && B->eng[r]->h_step % RESORT_POLL == 0;
+            for (int r = 0; r < R; r++) due |= !B->failed[r] && !nocut(B->eng[r]) && B->eng[r]->h_step > 0 && B->eng[r]->h_step % RESORT_POLL == 0;
             if (due) {
                 pick_leader();
                 if (!B->leader && !any_straggler()) return 0;
@@ -3100,7 +3227,8 @@ const char* blues_last_error(const BluesEngine* h) { return h ? h->err.c_str() :
 
 static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it) {
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) if (r != c && s->box[3 * r + c] != 0.0) E_FAIL(h, "only orthorhombic boxes are supported");
-    if (s->nonbonded_method != BLUES_NB_PME_DIRECT && s->nonbonded_method != BLUES_NB_PME) E_FAIL(h, "the GPU engine supports periodic systems only (BLUES_NB_PME_DIRECT, BLUES_NB_PME)");
+    if (s->nonbonded_method != BLUES_NB_PME_DIRECT && s->nonbonded_method != BLUES_NB_PME && s->nonbonded_method != BLUES_NB_NOCUTOFF) E_FAIL(h, "unknown nonbonded_method %d", s->nonbonded_method);
+    const bool no_cutoff = s->nonbonded_method == BLUES_NB_NOCUTOFF;
     if (s->nonbonded_method == BLUES_NB_PME) {
         h->pme = true; h->pme_order = s->pme_order; h->disp_corr = s->dispersion_correction;
         for (int d = 0; d < 3; d++) { h->pme_K[d] = s->pme_grid[d]; if (h->pme_K[d] < s->pme_order || h->pme_K[d] > 256) E_FAIL(h, "PME mesh %d along axis %d is outside [order, 256]", h->pme_K[d], d); }
@@ -3109,14 +3237,16 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
     const int n = h->n = s->n_atoms;
     if (n <= 0) E_FAIL(h, "empty system");
     h->box[0] = s->box[0]; h->box[1] = s->box[4]; h->box[2] = s->box[8];
-    h->nb_method = BLUES_NB_PME_DIRECT; h->cutoff = s->cutoff;   // (the direct-space kernels are the same under both methods)
-    h->alpha = s->ewald_alpha; h->sc_alpha = s->softcore_alpha;
-    for (int k = 0; k < 3; k++) if (h->box[k] < 2.0 * h->cutoff) E_FAIL(h, "box edge %g < 2*cutoff", h->box[k]);
+    h->nb_method = no_cutoff ? BLUES_NB_NOCUTOFF : BLUES_NB_PME_DIRECT; h->cutoff = no_cutoff ? 0.0 : s->cutoff;   // (the direct-space kernels are the same under both periodic methods)
+    h->alpha = no_cutoff ? 0.0 : s->ewald_alpha; h->sc_alpha = s->softcore_alpha;
     h->tune = g_tuning;
     if (h->tune.assume_batch > 0) h->batch_R = h->tune.assume_batch;
-    if (h->tune.skin > 0.0) { h->skin = h->tune.skin; h->skin_fixed = true; }
-    derive_margins(h);   // (again once the mobile set is known: sort_and_tile)
-    fit_ewald_poly(h->alpha, h->cutoff, &h->ewpoly);
+    if (!no_cutoff) {   // (NoCutoff: the box is stored and reported, nothing else -- no cutoff to fit in it, no margins, no Ewald sum)
+        for (int k = 0; k < 3; k++) if (h->box[k] < 2.0 * h->cutoff) E_FAIL(h, "box edge %g < 2*cutoff", h->box[k]);
+        if (h->tune.skin > 0.0) { h->skin = h->tune.skin; h->skin_fixed = true; }
+        derive_margins(h);   // (again once the mobile set is known: sort_and_tile)
+        fit_ewald_poly(h->alpha, h->cutoff, &h->ewpoly);
+    }
     h->annih_elec = s->annihilate_electrostatics; h->annih_ster = s->annihilate_sterics; h->remove_cm = s->remove_cm_motion;
     h->alch.assign(s->alchemical_atoms, s->alchemical_atoms + s->n_alchemical);
     if (h->alch.size() > 64) E_FAIL(h, "more than 64 alchemical atoms is not supported yet");
@@ -3229,6 +3359,7 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
     if (build_clusters(h, s)) return 1;
     // (the fragments of kernels_frag.h are cut when a layout first asks for them: sort_and_tile)
     try { if (build_bonded(h, s)) return 1; } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+    if (no_cutoff && nocut_layout(h)) return 1;
     return 0;
 }
 
@@ -3285,6 +3416,7 @@ static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
 
 // re-derive the tile layout and launch decomposition from the positions currently on the device
 static int relayout(BluesEngine* h) {
+    if (nocut(h)) return sort_and_tile(h);   // (nothing to lay out again: see nocut_layout)
     if (!h->have_positions) { h->sorted_ok = false; return 0; }
     if (flush_program(h)) return 1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -3549,7 +3681,7 @@ int blues_set_positions(BluesEngine* h, const double* xyz, int32_t n_atoms) {
     for (const HostCluster& c : h->clusters) for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0)
         for (int k = 0; k < 3; k++) {
             double d = st[3 * c.atoms[a] + k] - st[3 * c.atoms[0] + k];
-            st[3 * c.atoms[a] + k] -= h->box[k] * std::nearbyint(d / h->box[k]);
+            st[3 * c.atoms[a] + k] -= lattice_shift(h, k, d);
         }
     if (!h->sorted_ok) {   // first positions (or a box change pending): lay the tiles out from these coordinates
         HIP_OK(h, hipStreamSynchronize(h->stream));
@@ -3579,6 +3711,11 @@ int blues_set_box(BluesEngine* h, const double box[9]) {
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (nocut(h)) {   // stored and reported (blues_get_box); forces and energies do not depend on it
+        h->box[0] = box[0]; h->box[1] = box[4]; h->box[2] = box[8];
+        h->box_epoch++;
+        return 0;
+    }
     for (int k = 0; k < 3; k++) if (box[4 * k] < 2.0 * h->cutoff) E_FAIL(h, "box edge %g < 2*cutoff", box[4 * k]);   // (before anything is changed: a refused box leaves the engine as it was)
     h->box[0] = box[0]; h->box[1] = box[4]; h->box[2] = box[8];
     h->box_epoch++;
@@ -4108,7 +4245,7 @@ int blues_set_positions_from_snapshot_edited(BluesEngine* h, const BluesSnapshot
         for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0)   // one whole periodic image per cluster, as blues_set_positions stores them
             for (int k = 0; k < 3; k++) {
                 const double d = ed[3 * pos_of[c.atoms[a]] + k] - ed[3 * pos_of[c.atoms[0]] + k];
-                ed[3 * pos_of[c.atoms[a]] + k] -= h->box[k] * std::nearbyint(d / h->box[k]);
+                ed[3 * pos_of[c.atoms[a]] + k] -= lattice_shift(h, k, d);
             }
     }
     HIP_OK(h, hipSetDevice(h->device));
@@ -4168,6 +4305,7 @@ int blues_batch_create(BluesEngine* const* engines, int32_t count, BluesBatch** 
         if (engines[r]->device != engines[0]->device) { g_batch_create_error = "all engines of a batch must live on the same device"; return 2; }
         if (engines[r]->switch_mode != BLUES_SWITCH_NONE) { g_batch_create_error = "the switching integrators (switching_mode != 0) step one engine at a time: their energy bookkeeping is synchronous"; return 2; }
         for (int q = 0; q < r; q++) if (engines[q] == engines[r]) { g_batch_create_error = "duplicate engine handle"; return 2; }
+        if (nocut(engines[r]) != nocut(engines[0])) { g_batch_create_error = "a batch cannot mix NoCutoff (non-periodic) engines with periodic ones"; return 2; }
     }
     BluesBatch* B = new BluesBatch();
     hipSetDevice(engines[0]->device);
@@ -4360,7 +4498,7 @@ static int batch_restore_impl(BluesBatch* B, BluesSnapshot* const* snaps, int wh
                     for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0)
                         for (int k = 0; k < 3; k++) {
                             const double d = e0[3 * pos_of[c.atoms[a]] + k] - e0[3 * pos_of[c.atoms[0]] + k];
-                            e0[3 * pos_of[c.atoms[a]] + k] -= h->box[k] * std::nearbyint(d / h->box[k]);
+                            e0[3 * pos_of[c.atoms[a]] + k] -= lattice_shift(h, k, d);
                         }
                 }
             }

@@ -15,6 +15,10 @@ class EngineError(RuntimeError):
 
 class NativeEngine:
     def __init__(self, system: _abi.SystemData, integrator: _abi.IntegratorData, device=0):
+        # (checked before the library is touched: the engine has no custom forces, and without them it would run another potential)
+        if system.extras and any(system.extras.get(k) for k in ("custom_pair_mode", "centroid_bonds")):
+            raise EngineError("the GPU engine has no custom forces (SystemData.extras asks for %s): such a System runs on the oracle only"
+                              % ", ".join(sorted(k for k in ("custom_pair_mode", "centroid_bonds") if system.extras.get(k))))
         self._lib = load()
         sd, self._keep_s = system.to_desc()
         idesc, self._keep_i = integrator.to_desc()

@@ -36,7 +36,7 @@ extern "C" {
 #define BLUES_ABI_VERSION 6
 
 /* nonbonded_method */
-#define BLUES_NB_NOCUTOFF 0   /* oracle only: vacuum systems (vacDivaline, two-body checks) */
+#define BLUES_NB_NOCUTOFF 0   /* vacuum: every pair, bare Coulomb, no periodicity; the box is stored and has no effect */
 #define BLUES_NB_PME_DIRECT 1 /* periodic cutoff, erfc(alpha r)/r direct-space Coulomb + 12-6 LJ */
 #define BLUES_NB_PME 2        /* the same plus what OpenMM's NonbondedForce adds under nonbondedMethod=PME (reference
                                * blues/simulation.py:219, examples/rotmove_cuda.yml:20): smooth-PME reciprocal space on
