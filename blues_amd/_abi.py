@@ -9,11 +9,13 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 SWITCH_NONE, SWITCH_VV, SWITCH_GHMC = 0, 1, 2
 NB_NOCUTOFF = 0
 NB_PME_DIRECT = 1
 NB_PME = 2
+PAIR_STANDARD, PAIR_ETHYLENE = 0, 1      # BluesSystemDesc.custom_pair_mode
+MAX_CENTROID_BONDS, MAX_CENTROID_GROUP = 4, 8
 N_ENERGY_TERMS = 10
 N_STATS = 22
 N_BATCH_COUNTERS = 15
@@ -42,6 +44,8 @@ class BluesSystemDesc(C.Structure):
         ("annihilate_electrostatics", C.c_int32), ("annihilate_sterics", C.c_int32),
         ("remove_cm_motion", C.c_int32),
         ("pme_grid", C.c_int32 * 3), ("pme_order", C.c_int32), ("dispersion_correction", C.c_int32),
+        ("custom_pair_mode", C.c_int32), ("n_centroid_bonds", C.c_int32),
+        ("centroid_group_start", _ip), ("centroid_atoms", _ip), ("centroid_weights", _dp), ("centroid_k", _dp),
     ]
 
 
@@ -129,11 +133,38 @@ class SystemData:
     positions: np.ndarray = None         # (n,3) nm, optional initial coordinates
     residue_of_atom: np.ndarray = None   # optional bookkeeping for host-side selections
     names: list = None
-    extras: dict = None                  # oracle-only test extras (custom forces of the ethylene known-answer system); ignored by the engine
+    extras: dict = None                  # oracle-only test extras (custom forces of the ethylene known-answer system); refused by the engine, which takes them from the two typed fields below
+    custom_pair_mode: int = PAIR_STANDARD  # NB_NOCUTOFF only; PAIR_ETHYLENE: q/r^2 + lambda-scaled 12-6 between alchemical and non-alchemical atoms
+    centroid_bonds: tuple = ()           # NB_NOCUTOFF only; entries (idx1, w1, idx2, w2, k): E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w)
 
     @property
     def n_atoms(self):
         return int(len(self.mass))
+
+    def check_custom_forces(self):
+        """What blues_engine_create refuses about the two custom forces, raised before a library is loaded (ValueError)."""
+        mode, bonds, n = int(self.custom_pair_mode), tuple(self.centroid_bonds or ()), self.n_atoms
+        if mode not in (PAIR_STANDARD, PAIR_ETHYLENE):
+            raise ValueError("custom_pair_mode %d: the engine knows 0 (none) and 1 (the ethylene pair form)" % mode)
+        if (mode or bonds) and int(self.nonbonded_method) != NB_NOCUTOFF:
+            raise ValueError("custom forces (custom_pair_mode, centroid_bonds) need nonbonded_method = NoCutoff: they have no periodic form")
+        if mode == PAIR_ETHYLENE and len(np.asarray(self.alchemical_atoms).reshape(-1)) == 0:
+            raise ValueError("custom_pair_mode 1 acts between alchemical and non-alchemical atoms: the System has no alchemical atom")
+        if len(bonds) > MAX_CENTROID_BONDS:
+            raise ValueError("%d centroid bonds: at most %d" % (len(bonds), MAX_CENTROID_BONDS))
+        for b, bond in enumerate(bonds):
+            if len(bond) != 5:
+                raise ValueError("centroid bond %d: an entry is (idx1, w1, idx2, w2, k)" % b)
+            for idx, w in ((bond[0], bond[1]), (bond[2], bond[3])):
+                idx, w = np.asarray(idx).reshape(-1), np.asarray(w, dtype=np.float64).reshape(-1)
+                if len(idx) != len(w):
+                    raise ValueError("centroid bond %d: %d atoms but %d weights" % (b, len(idx), len(w)))
+                if len(idx) == 0 or len(idx) > MAX_CENTROID_GROUP:
+                    raise ValueError("centroid bond %d: a group of %d atoms (1 to %d)" % (b, len(idx), MAX_CENTROID_GROUP))
+                if np.any(idx < 0) or np.any(idx >= n):
+                    raise ValueError("centroid bond %d: atom index out of range" % b)
+                if not np.all(np.isfinite(w)) or w.sum() == 0.0:
+                    raise ValueError("centroid bond %d: the weights of a group sum to zero (or are not finite)" % b)
 
     def to_desc(self):
         """Returns (BluesSystemDesc, keepalive) -- keepalive owns the numpy buffers."""
@@ -179,6 +210,17 @@ class SystemData:
         for k in range(3):
             d.pme_grid[k] = int(self.pme_grid[k])
         d.pme_order = int(self.pme_order); d.dispersion_correction = int(bool(self.dispersion_correction))
+        # the custom forces (ABI 7): groups flattened, bond b = groups 2b and 2b + 1
+        d.custom_pair_mode = int(self.custom_pair_mode)
+        bonds = tuple(self.centroid_bonds or ())
+        start, atoms, weights = [0], [], []
+        for bond in bonds:
+            for idx, w in ((bond[0], bond[1]), (bond[2], bond[3])):
+                atoms.extend(int(i) for i in np.asarray(idx).reshape(-1)); weights.extend(float(x) for x in np.asarray(w, dtype=np.float64).reshape(-1))
+                start.append(len(atoms))
+        d.n_centroid_bonds = len(bonds)
+        put_i("centroid_group_start", start, (-1,)); put_i("centroid_atoms", atoms, (-1,))
+        put_f("centroid_weights", weights, (-1,)); put_f("centroid_k", [bond[4] for bond in bonds], (-1,))
         return d, keep
 
 

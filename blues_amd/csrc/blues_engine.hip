@@ -38,6 +38,8 @@
 #include "kernels_pme.h"
 #include "kernels_batch.h"
 #include "kernels_nocutoff.h"
+static_assert(CENT_GROUP == BLUES_MAX_CENTROID_GROUP, "a centroid-bond term has one place per atom the C-ABI allows in a group (kernels_bonded.h, build_bonded)");
+static_assert(T_CENT >= T_NTYPES, "T_CENT is an entry type only: it has no slot in the per-type arrays");
 
 static thread_local std::string g_create_error;
 // set-up cost accounting (diagnostic, blues_debug_setup_seconds): [0] blues_engine_create, [1] sort_and_tile, [2] its device uploads,
@@ -281,6 +283,7 @@ struct BluesEngine {
     bool fuse_forces = false, fast_step = true, fuse_big = false;  // fuse_big: measured slower (the alchemical role's 140 VGPRs and 36 KB LDS cap the occupancy of the nonbonded role)
     int k1_iw = 64;  // i-atoms per wave in the nonbonded kernel: 64 = classic tile kernel, 8/16 = sub-tile throughput kernel
     int k1_mode = 0;  // 0: tile kernel (lane = i-atom), 1: sub-tile kernel, 2: per-atom Verlet lists + LDS tile image (nonbonded_atom_body), 3: fragment lists (kernels_frag.h), 4: all pairs of a NoCutoff System (kernels_nocutoff.h)
+    int pair_mode = 0;   // BLUES_PAIR_*: 1 = the alchemical x environment pairs take the form of kernels_alch.h FORM 1 and are the only nonbonded pairs (NoCutoff)
     DBuf<double4> d_ncpar; int nc_blocks_f = 0, nc_blocks_e = 0;   // NoCutoff: per-atom parameters, blocks of the force / energy launches (nocut_layout)
     // fragment lists (every environment atom mobile): the static cut of the environment into fragments of <= 3 atoms
     // (build_fragments), the layout of the current sort, the lists
@@ -343,6 +346,7 @@ struct BluesEngine {
     DBuf<int> d_row_atom, d_row_start, d_ent_type, d_ent_term, d_ent_role;
     DBuf<int> d_term_atoms[T_NTYPES]; DBuf<double> d_term_params[T_NTYPES];
     int n_terms[T_NTYPES] = {0, 0, 0, 0, 0, 0}; int n_rows = 0; double restr_k = 0;
+    int n_cent = 0; DBuf<int> d_cent_atoms; DBuf<double> d_cent_params;   // harmonic centroid bonds (kernels_bonded.h: T_CENT, the CENT = true kernels)
     // pending integrate program
     Program prog; unsigned prog_draw_base = 0; int prog_trace = -1; bool tracing = false;
     // stats
@@ -759,6 +763,24 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
         }
         h->d_term_atoms[ty].upload(ta[ty]); h->d_term_params[ty].upload(tp[ty]);
     }
+    // centroid bonds (validated by create_impl): two groups of CENT_GROUP places each, unused places atom -1 / weight 0, then k; every
+    // mobile member owns an entry (type T_CENT, role = its place) behind its other entries
+    h->n_cent = s->n_centroid_bonds;
+    if (h->n_cent > 0) {
+        std::vector<int> at((size_t)h->n_cent * 2 * CENT_GROUP, -1); std::vector<double> w((size_t)h->n_cent * (2 * CENT_GROUP + 1), 0.0);
+        for (int b = 0; b < h->n_cent; b++) {
+            for (int g = 0; g < 2; g++) {
+                const int g0 = s->centroid_group_start[2 * b + g], g1 = s->centroid_group_start[2 * b + g + 1];
+                for (int q = g0; q < g1; q++) {
+                    const int place = g * CENT_GROUP + (q - g0), i = s->centroid_atoms[q];
+                    at[(size_t)b * 2 * CENT_GROUP + place] = i; w[(size_t)b * (2 * CENT_GROUP + 1) + place] = s->centroid_weights[q];
+                    if (h->T->mass[i] != 0.0) { rtype[i].push_back(T_CENT); rterm[i].push_back(b); rrole[i].push_back(place); }
+                }
+            }
+            w[(size_t)b * (2 * CENT_GROUP + 1) + 2 * CENT_GROUP] = s->centroid_k[b];
+        }
+        h->d_cent_atoms.upload(at); h->d_cent_params.upload(w);
+    }
     std::vector<int> row_atom, row_start(1, 0), et, ei, er;
     for (int i = 0; i < h->n; i++) if (!rtype[i].empty()) {
         row_atom.push_back(i);
@@ -769,7 +791,7 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
     { std::vector<int> row_of(h->n, -1); for (int r = 0; r < h->n_rows; r++) row_of[row_atom[r]] = r; h->d_row_of_orig.upload(row_of); h->h_row_of_orig = row_of; h->h_row_start = row_start; }
     h->d_fent.alloc((size_t)3 * std::max(1, h->n_entries));
     h->d_row_atom.upload(row_atom); h->d_row_start.upload(row_start); h->d_ent_type.upload(et); h->d_ent_term.upload(ei); h->d_ent_role.upload(er);
-    int total_terms = 0; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
+    int total_terms = h->n_cent; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     h->d_epart_b.alloc((size_t)((total_terms + 255) / 256 + 1) * T_NTYPES);
     // alchemical exception rows
     std::vector<int> es(1, 0), ep, eo; std::vector<double> epar;
@@ -1549,6 +1571,7 @@ static NcArgs make_nc_args(BluesEngine* h) {
 }
 // NoCutoff: the all-pairs kernel (kernels_nocutoff.h); a batch's leader launches it once for every member (gridDim.y)
 template <typename R, bool ENERGY> static int launch_nocut(BluesEngine* h) {
+    if (h->pair_mode == BLUES_PAIR_ETHYLENE) return 0;   // (environment x environment pairs do not interact in this form: no work, no launch; the force slab keeps its zeros, the energy has no partials -- energy_shape)
     const int nb = ENERGY ? h->nc_blocks_e : h->nc_blocks_f;
     if (batch_lead(h)) hipLaunchKernelGGL((k_nocutoff_b<R, ENERGY>), dim3(nb, h->batch->R()), dim3(NC_THREADS), 0, h->cur, h->batch->d_nc.p);
     else if (!batch_dry(h)) hipLaunchKernelGGL((k_nocutoff<R, ENERGY>), dim3(nb), dim3(NC_THREADS), 0, h->cur, make_nc_args(h));
@@ -1682,13 +1705,26 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
         const AlchDyn D = make_alch_dyn(A);
         const dim3 g(part == 2 ? std::min(nb * nrep, 8 * REBUILD_GRID) : nb * nrep), b(256);
         const int* work = h->batch->d_work.p;
+        if (h->pair_mode == BLUES_PAIR_ETHYLENE) {   // (NoCutoff: part is always 0)
+#define ALCH_B1(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M, 1>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep, (const int*)nullptr)
+            if (fast) { if (slot_mask == 5) ALCH_B1(true, 5); else if (slot_mask == 2) ALCH_B1(true, 2); else ALCH_B1(true, -1); }
+            else { if (slot_mask == 5) ALCH_B1(false, 5); else if (slot_mask == 2) ALCH_B1(false, 2); else ALCH_B1(false, -1); }
+#undef ALCH_B1
+            h->st_launches++;
+            HIP_OK(h, hipGetLastError());
+            return 0;
+        }
 #define ALCH_B(F, M) do { if (part == 2) hipLaunchKernelGGL((k_alchemical_stale_b<F, M>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, work); \
                           else hipLaunchKernelGGL((k_alchemical_b<F, M>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep, part == 1 ? work : (const int*)nullptr); } while (0)
         if (fast) { if (slot_mask == 5) ALCH_B(true, 5); else if (slot_mask == 2) ALCH_B(true, 2); else ALCH_B(true, -1); }
         else { if (slot_mask == 5) ALCH_B(false, 5); else if (slot_mask == 2) ALCH_B(false, 2); else ALCH_B(false, -1); }
 #undef ALCH_B
     } else if (!batch_dry(h)) {
-        if (fast) hipLaunchKernelGGL(k_alchemical<true>, dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
+        if (h->pair_mode == BLUES_PAIR_ETHYLENE) {
+            if (fast) hipLaunchKernelGGL((k_alchemical<true, 1>), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
+            else hipLaunchKernelGGL((k_alchemical<false, 1>), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
+        }
+        else if (fast) hipLaunchKernelGGL(k_alchemical<true>, dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
         else hipLaunchKernelGGL(k_alchemical<false>, dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
     }
     h->st_launches++;
@@ -1724,6 +1760,7 @@ static BondedArgs make_bonded_args(BluesEngine* h) {
     for (int k = 0; k < 3; k++) B.x[k] = h->d_x[k].p;
     B.box = make_box(h); B.periodic = h->nb_method == BLUES_NB_PME_DIRECT; B.fent = h->d_fent.p; B.n_entries = h->n_entries; B.n = h->n; B.epart = h->d_epart_b.p;
     B.n_mobile = (int)h->mobile.size(); B.n_noise = h->n_noise; B.mobile_atoms = h->d_mobile_atoms.p; B.noise = h->d_noise.p;
+    B.n_cent = h->n_cent; B.cent_atoms = h->d_cent_atoms.p; B.cent_params = h->d_cent_params.p;
     B.seed = h->seed; B.stream = (unsigned)h->replica * 4u; B.draw_base = h->h_draw; B.n_entry_blocks = (h->n_entries + 127) / 128; B.ctrl = h->ctrl_arg;
     return B;
 }
@@ -1734,8 +1771,12 @@ static int launch_bonded(BluesEngine* h, bool with_noise) {
     if (with_noise) { h->noise_draw_base = h->h_draw; h->noise_valid = true; }
     if (B.n_entry_blocks + nb_noise > 0) {
         BondedDyn D; D.draw_base = B.draw_base; D.n_entry_blocks = B.n_entry_blocks;
-        if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_entries_b, dim3(B.n_entry_blocks + nb_noise, h->batch->R()), dim3(128), 0, h->cur, h->batch->d_core.p, D);
-        else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_entries, dim3(B.n_entry_blocks + nb_noise), dim3(128), 0, h->cur, B);
+        if (h->n_cent > 0) {   // (centroid bonds: the instantiations that know the entry type)
+            if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_entries_b<true>, dim3(B.n_entry_blocks + nb_noise, h->batch->R()), dim3(128), 0, h->cur, h->batch->d_core.p, D);
+            else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_entries<true>, dim3(B.n_entry_blocks + nb_noise), dim3(128), 0, h->cur, B);
+        }
+        else if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_entries_b<false>, dim3(B.n_entry_blocks + nb_noise, h->batch->R()), dim3(128), 0, h->cur, h->batch->d_core.p, D);
+        else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_entries<false>, dim3(B.n_entry_blocks + nb_noise), dim3(128), 0, h->cur, B);
         h->st_launches++;
     }
     HIP_OK(h, hipGetLastError());
@@ -2220,6 +2261,10 @@ static int force_pass(BluesEngine* h, int base_L) {
         if (rc) return 1;
     }
     h->lists_forced = false;
+    // (the fused force kernels, the fused finalize and every periodic form run the bonded entries and the alchemical pairs WITHOUT the custom
+    // forces -- CENT = false, FORM 0: an engine that carries them must be on the decomposed NoCutoff path, where nocut_layout put it)
+    if ((h->n_cent > 0 || h->pair_mode != BLUES_PAIR_STANDARD) && (h->k1_mode != 4 || h->fuse_forces || h->fuse_big || h->k2_dense || h->use_graph))
+        E_FAIL(h, "internal: an engine with custom forces left the decomposed NoCutoff path (k1_mode %d, fuse_forces %d, fuse_big %d, k2_dense %d)", h->k1_mode, (int)h->fuse_forces, (int)h->fuse_big, (int)h->k2_dense);
     if (h->fuse_forces && h->wpb == 4) {
         rc = h->precision == 0 ? launch_forces_fused<float>(h, ls, le) : launch_forces_fused<double>(h, ls, le);
         if (rc) return 1;
@@ -2337,7 +2382,8 @@ static EnergyShape energy_shape(const BluesEngine* h) {
     g.off_frozen = (size_t)std::max(1, h->n_itiles) * h->npart * 2 * subs;
     if (h->k1_mode == 3) { g.nw = h->frag_nwg; g.off_frozen = (size_t)2 * h->frag_nwg; }   // one (LJ, Coulomb) pair per workgroup of the fragment kernel
     if (h->k1_mode == 4) { g.nw = h->nc_blocks_e; g.off_frozen = (size_t)2 * h->nc_blocks_e; }   // one (LJ, Coulomb) pair per block of the all-pairs kernel (it has every pair: no frozen-frozen constant)
-    int total_terms = 0; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
+    if (h->pair_mode == BLUES_PAIR_ETHYLENE) g.nw = 0;   // (the all-pairs kernel is not launched: launch_nocut)
+    int total_terms = h->n_cent; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     g.nbb = (total_terms + 255) / 256; g.nfb = (h->n + FROZEN_TILE - 1) / FROZEN_TILE;
     return g;
 }
@@ -2362,8 +2408,12 @@ static int energy_launch(BluesEngine* h) {
     if (launch_pme(h, 1)) return 1;
     const EnergyShape g = energy_shape(h);
     if (g.nbb > 0) {
-        if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
-        else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
+        if (h->n_cent > 0) {
+            if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b<true>, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
+            else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy<true>, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
+        }
+        else if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b<false>, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
+        else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy<false>, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
         h->st_launches++;
     }
     HIP_OK(h, hipGetLastError());
@@ -2806,6 +2856,7 @@ static BatchSig batch_sig(const BluesEngine* h) {
 // static shape of a member: launch geometry and protocol.  All members must agree.
 static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const char** why) {
     if (nocut(a) != nocut(b)) { *why = "nonbonded method (a NoCutoff engine and a periodic one cannot share a batch)"; return false; }
+    if (a->pair_mode != b->pair_mode || a->n_cent != b->n_cent) { *why = "custom forces (members with and without the custom pair form or centroid bonds cannot share a batch)"; return false; }
 #define BC(f) if (a->f != b->f) { *why = #f; return false; }
     BC(device) BC(n) BC(precision) BC(nsteps) BC(nprop) BC(n_lambda) BC(split) BC(remove_cm) BC(dt) BC(gamma) BC(kT) BC(tol) BC(prop_min) BC(prop_max)
     BC(n_itiles) BC(n_tiles) BC(jcap) BC(n_islots) BC(pool_cap) BC(PA) BC(k2_nblocks_env) BC(k2_jiter) BC(seg_len) BC(waves_tile) BC(wpb) BC(npart)
@@ -3248,6 +3299,23 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
         fit_ewald_poly(h->alpha, h->cutoff, &h->ewpoly);
     }
     h->annih_elec = s->annihilate_electrostatics; h->annih_ster = s->annihilate_sterics; h->remove_cm = s->remove_cm_motion;
+    // the custom forces (ABI 7): NoCutoff only
+    if (s->custom_pair_mode != BLUES_PAIR_STANDARD && s->custom_pair_mode != BLUES_PAIR_ETHYLENE) E_FAIL(h, "custom_pair_mode %d: the engine knows 0 (none) and 1 (the ethylene pair form)", s->custom_pair_mode);
+    if ((s->custom_pair_mode != BLUES_PAIR_STANDARD || s->n_centroid_bonds != 0) && !no_cutoff) E_FAIL(h, "custom forces (custom_pair_mode, centroid bonds) need nonbonded_method = NoCutoff: they have no periodic form");
+    if (s->custom_pair_mode == BLUES_PAIR_ETHYLENE && s->n_alchemical <= 0) E_FAIL(h, "custom_pair_mode 1 acts between alchemical and non-alchemical atoms: the System has no alchemical atom");
+    if (s->n_centroid_bonds < 0 || s->n_centroid_bonds > BLUES_MAX_CENTROID_BONDS) E_FAIL(h, "%d centroid bonds: at most %d", s->n_centroid_bonds, BLUES_MAX_CENTROID_BONDS);
+    if (s->n_centroid_bonds > 0 && (!s->centroid_group_start || !s->centroid_atoms || !s->centroid_weights || !s->centroid_k)) E_FAIL(h, "centroid bonds without their arrays");
+    for (int b = 0; b < s->n_centroid_bonds; b++) for (int g = 0; g < 2; g++) {
+        const int g0 = s->centroid_group_start[2 * b + g], g1 = s->centroid_group_start[2 * b + g + 1];
+        if ((b == 0 && g == 0 && g0 != 0) || g1 - g0 < 1 || g1 - g0 > BLUES_MAX_CENTROID_GROUP) E_FAIL(h, "centroid bond %d: a group of %d atoms (1 to %d)", b, g1 - g0, BLUES_MAX_CENTROID_GROUP);
+        double W = 0.0;
+        for (int q = g0; q < g1; q++) {
+            if (s->centroid_atoms[q] < 0 || s->centroid_atoms[q] >= n) E_FAIL(h, "centroid bond %d: atom index out of range", b);
+            W += s->centroid_weights[q];
+        }
+        if (!(W != 0.0) || !std::isfinite(W)) E_FAIL(h, "centroid bond %d: the weights of a group sum to zero (or are not finite)", b);
+    }
+    h->pair_mode = s->custom_pair_mode;
     h->alch.assign(s->alchemical_atoms, s->alchemical_atoms + s->n_alchemical);
     if (h->alch.size() > 64) E_FAIL(h, "more than 64 alchemical atoms is not supported yet");
     for (int a : h->alch) if (a < 0 || a >= n) E_FAIL(h, "alchemical atom out of range");
@@ -4306,6 +4374,7 @@ int blues_batch_create(BluesEngine* const* engines, int32_t count, BluesBatch** 
         if (engines[r]->switch_mode != BLUES_SWITCH_NONE) { g_batch_create_error = "the switching integrators (switching_mode != 0) step one engine at a time: their energy bookkeeping is synchronous"; return 2; }
         for (int q = 0; q < r; q++) if (engines[q] == engines[r]) { g_batch_create_error = "duplicate engine handle"; return 2; }
         if (nocut(engines[r]) != nocut(engines[0])) { g_batch_create_error = "a batch cannot mix NoCutoff (non-periodic) engines with periodic ones"; return 2; }
+        if (engines[r]->pair_mode != engines[0]->pair_mode || engines[r]->n_cent != engines[0]->n_cent) { g_batch_create_error = "a batch cannot mix engines with and without custom forces (custom pair form, centroid bonds)"; return 2; }
     }
     BluesBatch* B = new BluesBatch();
     hipSetDevice(engines[0]->device);

@@ -71,8 +71,16 @@ __device__ inline bool excluded_sorted(const int* ex_start, const int* ex_idx, i
 // FAST: the mixed-precision mode's math (device_common.h, fast fp64 forms); false = libm forms, the reference-grade path
 // MASK: the force slot mask known at compile time (5 and 2 are what "H V R O R V H" asks for, see force_pass), so that the
 // force arithmetic, accumulators and reductions of the other slots are not even compiled in; -1 = use A.slot_mask
+// FORM: 0 = the pair forms above; 1 = the pair form of BLUES_PAIR_ETHYLENE (include/blues_engine.h), a NoCutoff System's
+// CustomNonbondedForce between its alchemical and its non-alchemical atoms:
+//     q_i q_j / r^2 + 4 eps ((sig / r)^12 - (sig / r)^6),   sig = 0.5 (sigma_i + sigma_j) ls,   eps = sqrt(eps_i eps_j) le
+// Both lambdas move the 12-6 part, so it is formed per slot from ls[s] AND le[s] and lands in the per-slot sterics S0..S2 (neither
+// shortcut of the FAST path holds); q / r^2 depends on no lambda and lands in const_coul.  sig = 0 gives an exact 0, no softcore is
+// needed.  The alchemical x alchemical pairs do not interact in this form: the last block evaluates the exception rows only.
+// Energies fp64 in both precisions (they are the protocol work); the force scale is formed in fp64 with them and its components are
+// FT, as in the env blocks of form 0.
 // Returns false when the (env) block had no list entries left, i.e. every later block is empty too.
-template <bool FAST, int MASK = -1>
+template <bool FAST, int MASK = -1, int FORM = 0>
 __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id) {
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
     if (A.ctrl) {
@@ -162,7 +170,20 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                     const double qq = Ar.q * J.q;
                     double fc;
                     hit = true;
-                    if (FAST && A.pme) {
+                    if constexpr (FORM == 1) {
+                        const double inv_r2 = 1.0 / r2, qr2 = qq * inv_r2;
+                        e[5] += qr2;
+                        fc = 2.0 * qr2 * inv_r2;   // -d(q / r^2)/dr / r
+#pragma unroll
+                        for (int s = 0; s < 3; s++) {
+                            const double sg = sig * A.ls[s], ep4 = 4.0 * eps * A.le[s];
+                            const double sr2 = sg * sg * inv_r2, sr6 = sr2 * sr2 * sr2;
+                            e[1 + s] += ep4 * (sr6 * sr6 - sr6);
+                            if (MASK >= 0 && !((MASK >> s) & 1)) continue;
+                            const FT ft = (FT)(fc + ep4 * (12.0 * sr6 * sr6 - 6.0 * sr6) * inv_r2);
+                            f[s][0] = ft * (FT)d[0]; f[s][1] = ft * (FT)d[1]; f[s][2] = ft * (FT)d[2];
+                        }
+                    } else if (FAST && A.pme) {
                         // Two things the schedule makes common (reference blues/simulation.py:654-659: sterics move only for
                         // 0.2 < lambda < 0.8, electrostatics only outside) are checked on the actual slot values, not assumed:
                         // with lambda_electrostatics = 0 in every slot the Coulomb sum multiplies zeros (energy le * C, force
@@ -234,7 +255,8 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
     } else {
         // ---- alchemical x alchemical pairs: thread (a2, b) with b fastest
         const int rows_per_iter = 256 / PA;
-        for (int a0 = 0; a0 < A.n_alch; a0 += rows_per_iter) {
+        if constexpr (FORM == 1) { if (tid < 64) for (int q = 0; q < 9; q++) s_self[0][q][tid] = 0.0; }   // (no alchemical x alchemical pairs in this form)
+        for (int a0 = 0; FORM == 0 && a0 < A.n_alch; a0 += rows_per_iter) {
             const int a2 = a0 + tid / PA, b = a;
             double g[3][3];
 #pragma unroll
@@ -365,11 +387,11 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
 // not depend on nphys.  (Sized for the list's CAPACITY, 4 of 5 blocks of a launch were empty and each still held an
 // occupancy slot for three dependent loads.)
 #define K2_PHYS 24
-template <bool FAST, int MASK = -1>
+template <bool FAST, int MASK = -1, int FORM = 0>
 __device__ __forceinline__ void alchemical_blocks(AlchArgs& A, const int p, const int nphys) {
-    if (p >= nphys) { alchemical_body<FAST, MASK>(A, A.nblocks_env); return; }
+    if (p >= nphys) { alchemical_body<FAST, MASK, FORM>(A, A.nblocks_env); return; }
     for (int lb = p; lb < A.nblocks_env; lb += nphys) {
-        if (!alchemical_body<FAST, MASK>(A, lb)) return;
+        if (!alchemical_body<FAST, MASK, FORM>(A, lb)) return;
         __syncthreads();   // the next logical block reuses the LDS staging and partial arrays
     }
 }
@@ -891,5 +913,5 @@ __global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32(AlchArgs 
 template <int MASK>
 __global__ void __launch_bounds__(K2D_THREADS) k_alchemical_dense(AlchArgs A) { alchemical_dense_body<MASK>(A); }
 
-template <bool FAST>
-__global__ void __launch_bounds__(256) k_alchemical(AlchArgs A) { alchemical_blocks<FAST>(A, blockIdx.x, gridDim.x - 1); }
+template <bool FAST, int FORM = 0>
+__global__ void __launch_bounds__(256) k_alchemical(AlchArgs A) { alchemical_blocks<FAST, -1, FORM>(A, blockIdx.x, gridDim.x - 1); }

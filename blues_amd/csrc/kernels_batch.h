@@ -232,13 +232,13 @@ __global__ void __launch_bounds__(256) k_gather_pme_e_b(const RepNb<R>* __restri
 
 // stale: null = every member; else the work list of the rebuild (k_gather_stale_b): the members that rebuild are left to
 // k_alchemical_stale_b, which follows the rebuild of the group lists (the alchemical tile's records are among them)
-template <bool FAST, int MASK>
+template <bool FAST, int MASK, int FORM = 0>
 __global__ void __launch_bounds__(256, 3) k_alchemical_b(const RepCore* __restrict__ reps, AlchDyn d, int nb, int nrep, const int* __restrict__ stale) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     if (!reps[rep].active) return;
     if (stale && stale[1 + nrep + rep]) return;
     AlchArgs A = reps[rep].al; apply_dyn(A, d);
-    alchemical_blocks<FAST, MASK>(A, bx, nb - 1);
+    alchemical_blocks<FAST, MASK, FORM>(A, bx, nb - 1);
 }
 
 template <bool FAST, int MASK>
@@ -274,10 +274,11 @@ __global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32_b(const R
     alchemical_dense32_body<MASK>(A);
 }
 
+template <bool CENT = false>
 __global__ void __launch_bounds__(128) k_bonded_entries_b(const RepCore* __restrict__ reps, BondedDyn d) {
     if (!reps[blockIdx.y].active) return;
     BondedArgs B = reps[blockIdx.y].bo; apply_dyn(B, d, reps[blockIdx.y].draw_delta);
-    bonded_entries_body(B, blockIdx.x, 128);
+    bonded_entries_body<CENT>(B, blockIdx.x, 128);
 }
 
 template <bool LEAN>
@@ -418,10 +419,11 @@ __global__ void k_zero_acc_b(DevAccum* const* __restrict__ acc, int R) {
     if (r < R && acc[r]) { DevAccum z; z.protocol_work = z.dE_last = z.heat = 0.0; z.e_slot[0] = z.e_slot[1] = z.e_slot[2] = 0.0; *acc[r] = z; }
 }
 
+template <bool CENT = false>
 __global__ void __launch_bounds__(256) k_bonded_energy_b(const RepCore* __restrict__ reps) {
     if (!reps[blockIdx.y].active) return;
     const BondedArgs B = reps[blockIdx.y].bo;
-    bonded_energy_body(B);
+    bonded_energy_body<CENT>(B);
 }
 
 // kinetic energy of every member: one block each, fixed summation order -> ke[r]

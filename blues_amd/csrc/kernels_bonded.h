@@ -1,5 +1,5 @@
-// kernels_bonded.h -- harmonic bonds/angles, periodic torsions, env-env 1-4 exceptions and
-// the positional restraint (K3/K4), fp64, gather form.
+// kernels_bonded.h -- harmonic bonds/angles, periodic torsions, env-env 1-4 exceptions, the
+// positional restraint and harmonic centroid bonds (K3/K4), fp64, gather form.
 //
 // OpenMM's HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce / NonbondedForce
 // exceptions / CustomExternalForce('k_restr*periodicdistance(x,y,z,x0,y0,z0)^2',
@@ -11,6 +11,11 @@
 #include "device_common.h"
 
 enum { T_BOND = 0, T_ANGLE = 1, T_TORSION = 2, T_EXC = 3, T_RESTR = 4, T_EWEX = 5, T_NTYPES = 6 };   // T_EWEX: Ewald correction of an excluded pair (BLUES_NB_PME)
+// Harmonic centroid bonds (CustomCentroidBondForce '0.5*k*distance(g1,g2)^2' of a NoCutoff System): an ENTRY type only.  Its terms live in
+// arrays of their own (BondedArgs::cent_*), its energy is booked with the restraint's, and only the CENT = true instantiations of the
+// templates below know it -- the CENT = false ones, which every System without such bonds runs, are the code they were before it existed.
+enum { T_CENT = T_NTYPES };   // (the first value past the per-type arrays; blues_engine.hip asserts it stays there)
+#define CENT_GROUP 8   // places per group (BLUES_MAX_CENTROID_GROUP); a term is two groups, unused places hold atom -1 and weight 0
 
 struct BondedArgs {
     int n_rows;
@@ -38,6 +43,8 @@ struct BondedArgs {
     unsigned long long seed; unsigned stream, draw_base;
     int n_entry_blocks;
     const DevCtrl* ctrl;
+    // centroid bonds: 2 * CENT_GROUP atoms and 2 * CENT_GROUP weights + k per term
+    int n_cent; const int* cent_atoms; const double* cent_params;
 };
 
 __device__ inline void mi3(const BondedArgs& B, double d[3]) {
@@ -49,8 +56,32 @@ __device__ inline void cross3(const double a[3], const double b[3], double c[3])
 __device__ inline double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // energy of term (type, idx); if role >= 0 also the force on the atom in that role
+template <bool CENT = false>
 __device__ inline double bonded_term(const BondedArgs& B, int type, int idx, int role, double F[3]) {
     F[0] = F[1] = F[2] = 0.0;
+    if constexpr (CENT) {
+        if (type == T_CENT) {  // E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w): explicit weights, summed in the groups' order; never periodic
+            const int* q = B.cent_atoms + 2 * CENT_GROUP * idx;
+            const double* w = B.cent_params + (2 * CENT_GROUP + 1) * idx;
+            const double kk = w[2 * CENT_GROUP];
+            double c[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, W[2] = {0.0, 0.0};
+            for (int g = 0; g < 2; g++)
+                for (int s = 0; s < CENT_GROUP; s++) {
+                    const int a = q[g * CENT_GROUP + s];
+                    if (a < 0) break;
+                    const double ws = w[g * CENT_GROUP + s];
+                    W[g] += ws;
+                    for (int m = 0; m < 3; m++) c[g][m] += ws * B.x[m][a];
+                }
+            double d[3];
+            for (int m = 0; m < 3; m++) d[m] = c[0][m] / W[0] - c[1][m] / W[1];
+            if (role >= 0) {   // role = the member's place: group 1 is pulled towards group 2 and the other way round
+                const int g = role / CENT_GROUP;
+                for (int m = 0; m < 3; m++) { const double f = kk * d[m] * w[role] / W[g]; F[m] = g == 0 ? -f : f; }
+            }
+            return 0.5 * kk * dot3(d, d);
+        }
+    }
     if (type == T_BOND) {
         const int i = B.atoms[T_BOND][2 * idx], j = B.atoms[T_BOND][2 * idx + 1];
         const double r0 = B.params[T_BOND][2 * idx], k = B.params[T_BOND][2 * idx + 1];
@@ -140,6 +171,7 @@ __device__ inline double bonded_term(const BondedArgs& B, int type, int idx, int
 // one thread per (row, entry): the force of one term on one of its mobile atoms -> fent[3][n_entries];
 // blocks past n_entry_blocks draw the N(0,1) numbers of the coming O substeps (counter-based, so they can be
 // produced before the velocities they will be applied to exist).
+template <bool CENT = false>
 __device__ __forceinline__ void bonded_entries_body(const BondedArgs& B, const int block_id, const int nthreads) {
     if (block_id >= B.n_entry_blocks) {
         const int g = (block_id - B.n_entry_blocks) * nthreads + threadIdx.x;
@@ -154,13 +186,16 @@ __device__ __forceinline__ void bonded_entries_body(const BondedArgs& B, const i
     const int e = block_id * nthreads + threadIdx.x;
     if (e >= B.n_entries) return;
     double F[3];
-    bonded_term(B, B.ent_type[e], B.ent_term[e], B.ent_role[e], F);
+    bonded_term<CENT>(B, B.ent_type[e], B.ent_term[e], B.ent_role[e], F);
     B.fent[e] = F[0]; B.fent[B.n_entries + e] = F[1]; B.fent[2 * B.n_entries + e] = F[2];
 }
 
-__global__ void __launch_bounds__(128) k_bonded_entries(BondedArgs B) { bonded_entries_body(B, blockIdx.x, 128); }
+template <bool CENT = false>
+__global__ void __launch_bounds__(128) k_bonded_entries(BondedArgs B) { bonded_entries_body<CENT>(B, blockIdx.x, 128); }
 
 // energy of every term (frozen ones included): per-block partial sums per type
+// (CENT: the centroid bonds follow the six types; their energy goes into the restraint's partial -- both are energy term 7)
+template <bool CENT = false>
 __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
     const int gid = blockIdx.x * 256 + threadIdx.x;
     double e[T_NTYPES] = {0, 0, 0, 0, 0, 0};
@@ -170,10 +205,15 @@ __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
         if (idx >= 0 && idx < B.n_terms[ty]) { double F[3]; e[ty] = bonded_term(B, ty, idx, -1, F); }
         base += B.n_terms[ty];
     }
+    if constexpr (CENT) {
+        const int idx = gid - base;
+        if (idx >= 0 && idx < B.n_cent) { double F[3]; e[T_RESTR] += bonded_term<true>(B, T_CENT, idx, -1, F); }
+    }
     __shared__ double s[4][T_NTYPES];
     for (int ty = 0; ty < T_NTYPES; ty++) { double v = wave_sum(e[ty]); if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6][ty] = v; }
     __syncthreads();
     if (threadIdx.x < T_NTYPES) B.epart[blockIdx.x * T_NTYPES + threadIdx.x] = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x];
 }
 
-__global__ void __launch_bounds__(256) k_bonded_energy(BondedArgs B) { bonded_energy_body(B); }
+template <bool CENT = false>
+__global__ void __launch_bounds__(256) k_bonded_energy(BondedArgs B) { bonded_energy_body<CENT>(B); }

@@ -15,10 +15,16 @@ class EngineError(RuntimeError):
 
 class NativeEngine:
     def __init__(self, system: _abi.SystemData, integrator: _abi.IntegratorData, device=0):
-        # (checked before the library is touched: the engine has no custom forces, and without them it would run another potential)
+        # (checked before the library is touched: the untyped extras are the oracle's channel; the engine takes its custom forces from
+        # SystemData.custom_pair_mode / .centroid_bonds, and ignoring the extras would run another potential)
         if system.extras and any(system.extras.get(k) for k in ("custom_pair_mode", "centroid_bonds")):
-            raise EngineError("the GPU engine has no custom forces (SystemData.extras asks for %s): such a System runs on the oracle only"
+            raise EngineError("the GPU engine takes no custom forces from SystemData.extras (it asks for %s): set the typed fields "
+                              "SystemData.custom_pair_mode / SystemData.centroid_bonds instead"
                               % ", ".join(sorted(k for k in ("custom_pair_mode", "centroid_bonds") if system.extras.get(k))))
+        try:
+            system.check_custom_forces()
+        except ValueError as e:
+            raise EngineError(str(e))
         self._lib = load()
         sd, self._keep_s = system.to_desc()
         idesc, self._keep_i = integrator.to_desc()

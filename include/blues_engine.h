@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BLUES_ABI_VERSION 6
+#define BLUES_ABI_VERSION 7
 
 /* nonbonded_method */
 #define BLUES_NB_NOCUTOFF 0   /* vacuum: every pair, bare Coulomb, no periodicity; the box is stored and has no effect */
@@ -97,7 +97,26 @@ typedef struct BluesSystemDesc {
     int32_t pme_grid[3];           /* mesh points along a,b,c: ceil(2 alpha L / (3 tol^(1/5))) for ewaldErrorTolerance tol */
     int32_t pme_order;             /* B-spline order; OpenMM uses 5 */
     int32_t dispersion_correction; /* NonbondedForce.getUseDispersionCorrection() (OpenMM's default: on) */
+    /* ABI 7: the two custom forces of the reference's known-answer System (blues/tests/data/ethylene_system.xml).  BLUES_NB_NOCUTOFF
+     * only: blues_engine_create refuses either of them on a periodic System. */
+    int32_t custom_pair_mode;      /* BLUES_PAIR_* */
+    int32_t n_centroid_bonds;      /* CustomCentroidBondForce '0.5*k*distance(g1,g2)^2': E = 0.5 k |c1 - c2|^2, c_g = sum(w x) / sum(w), no
+                                    * periodicity; booked with the restraint (energy term 7).  At most BLUES_MAX_CENTROID_BONDS bonds of two
+                                    * groups of at most BLUES_MAX_CENTROID_GROUP atoms each; a group's weights may not sum to 0 */
+    const int32_t *centroid_group_start; /* [2*n_centroid_bonds+1] bond b: group 1 = entries [start[2b], start[2b+1]), group 2 = [start[2b+1], start[2b+2]) */
+    const int32_t *centroid_atoms;       /* [start[2*n_centroid_bonds]] */
+    const double *centroid_weights;      /* [start[2*n_centroid_bonds]] explicit weights (OpenMM's default, the particle's mass, is the caller's to fill in) */
+    const double *centroid_k;            /* [n_centroid_bonds] kJ/mol/nm^2 */
 } BluesSystemDesc;
+#define BLUES_PAIR_STANDARD 0 /* the alchemical pair forms above */
+#define BLUES_PAIR_ETHYLENE 1 /* every non-excluded pair of one alchemical and one non-alchemical atom, and no other pair, interacts by
+                               *   q_i q_j / r^2 + 4 eps ((sig/r)^12 - (sig/r)^6),  sig = 0.5 (sigma_i + sigma_j) lambda_sterics,
+                               *                                                     eps = sqrt(eps_i eps_j) lambda_electrostatics
+                               * (no Coulomb constant, no softcore, no cutoff; q / r^2 is scaled by no lambda and booked in energy term 6, the
+                               * 12-6 part in term 5, term 3 is 0).  softcore_alpha and the annihilate_* flags have no effect; exceptions keep
+                               * the forms they have without the mode.  Needs at least one alchemical atom. */
+#define BLUES_MAX_CENTROID_BONDS 4
+#define BLUES_MAX_CENTROID_GROUP 8
 
 /*
  * Parameters of AlchemicalExternalLangevinIntegrator.__init__

@@ -4,7 +4,9 @@ NoCutoff (vacuum) stepping through NativeBatch: NCMC switch steps of the referen
 vacDivaline (alchemical atoms 22-31, the side chain SideChainMove(struct, [1]) selects) at R = 1024.  Prints ONE JSON line: ns/day
 per configuration (R chains x simulated time per wall-clock time) and the environment pairs the all-pairs kernel evaluates per step
 (pairs_per_step: each pair of a mobile environment atom with every atom, from both ends; divide by the kernel's time from a
-`rocprofv3 --kernel-trace --stats` run of this script for the achieved pair rate)."""
+`rocprofv3 --kernel-trace --stats` run of this script for the achieved pair rate).
+--only ethylene:R runs the reference's known-answer System (tests/ethylene.py: 8 atoms, custom pair form + centroid bond, dt 1 fs,
+200 K) instead: its environment atoms are frozen and the all-pairs kernel is not launched (pairs_per_step 0)."""
 import argparse
 import json
 import os
@@ -32,11 +34,18 @@ def nocutoff_system(name):
 
 def run(name, R, steps, warmup, nsteps_nc):
     from blues_amd.engine import NativeBatch, NativeEngine
-    s = nocutoff_system(name)
+    custom = name == "ethylene"
+    if custom:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import ethylene
+        s, proto = ethylene.load()
+    else:
+        s = nocutoff_system(name)
+    dt, temperature = (proto["dt"], proto["temperature"]) if custom else (DT, 300.0)
     rng = np.random.RandomState(7)
     engs = []
     for r in range(R):
-        d = integrators.generateNCMCIntegrator(nstepsNC=nsteps_nc, dt=DT, temperature=300.0, seed=100 + r).to_data(precision=0, replica=r)
+        d = integrators.generateNCMCIntegrator(nstepsNC=nsteps_nc, dt=dt, temperature=temperature, seed=100 + r).to_data(precision=0, replica=r)
         e = NativeEngine(s, d)
         e.set_velocities(0.3 * rng.standard_normal((s.n_atoms, 3)) * (s.mass[:, None] > 0))
         engs.append(e)
@@ -50,7 +59,7 @@ def run(name, R, steps, warmup, nsteps_nc):
     st = b.stats()
     mobile_env = int(((s.mass > 0) & ~np.isin(np.arange(s.n_atoms), s.alchemical_atoms)).sum())
     out = {"system": name, "R": R, "atoms": s.n_atoms, "steps": steps, "us_per_step": 1e6 * sec / steps,
-           "ns_per_day": R * steps * DT * 1e-3 / sec * 86400.0, "pairs_per_step": R * mobile_env * s.n_atoms,
+           "ns_per_day": R * steps * dt * 1e-3 / sec * 86400.0, "pairs_per_step": 0 if custom else R * mobile_env * s.n_atoms, "dt_ps": dt,   # (each result carries its own timestep)
            "lockstep_steps": st["lockstep_steps"], "fallback_steps": st["fallback_steps"], "nonbonded_kernel": engs[0].stats()["nonbonded_kernel"]}
     b.close()
     for e in engs:
@@ -68,7 +77,10 @@ def main():
     cfgs = [(c.split(":")[0], int(c.split(":")[1])) for c in a.only.split(",")] if a.only else DEFAULT
     nsteps_nc = a.steps + a.warmup   # (one switch covers the measurement: no switch end in the timed steps)
     res = [run(n, R, a.steps, a.warmup, nsteps_nc) for n, R in cfgs]
-    print(json.dumps({"metric": "NoCutoff NCMC ns/day through NativeBatch (mixed precision)", "unit": "ns/day", "dt_ps": DT, "results": res}))
+    out = {"metric": "NoCutoff NCMC ns/day through NativeBatch (mixed precision)", "unit": "ns/day", "results": res}
+    if all(r["dt_ps"] == DT for r in res):   # (the ethylene workload steps at its own 1 fs: every result carries its dt_ps)
+        out = {"metric": out["metric"], "unit": "ns/day", "dt_ps": DT, "results": res}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
