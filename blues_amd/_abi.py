@@ -9,7 +9,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 SWITCH_NONE, SWITCH_VV, SWITCH_GHMC = 0, 1, 2
 NB_NOCUTOFF = 0
 NB_PME_DIRECT = 1
@@ -70,11 +70,10 @@ class BluesTuning(C.Structure):
         ("skin", C.c_double), ("prune_margin", C.c_double), ("jcap_scale", C.c_double), ("acap_scale", C.c_double),
         ("k1_mode", C.c_int32), ("list_group", C.c_int32), ("sub_iw", C.c_int32), ("sub_chunks", C.c_int32),
         ("seg_len", C.c_int32), ("waves_per_block", C.c_int32), ("k2_jiter", C.c_int32),
-        ("fuse_forces", C.c_int32), ("fuse_big", C.c_int32), ("fast_step", C.c_int32), ("slot_mask", C.c_int32),
-        ("fork", C.c_int32), ("use_graph", C.c_int32), ("graph_units", C.c_int32), ("graph_fork", C.c_int32),
+        ("fuse_forces", C.c_int32), ("fast_step", C.c_int32), ("fork", C.c_int32),
         ("batch_sync_lists", C.c_int32), ("force_lists", C.c_int32), ("no_sphere", C.c_int32),
         ("pme_general", C.c_int32), ("debug_lists", C.c_int32), ("assume_batch", C.c_int32), ("k1_threads", C.c_int32),
-        ("k2_dense", C.c_int32), ("k2_early", C.c_int32), ("fuse_finalize", C.c_int32), ("host_threads", C.c_int32),
+        ("k2_dense", C.c_int32), ("fuse_finalize", C.c_int32), ("host_threads", C.c_int32),
         ("pack_clusters", C.c_int32),
     ]
 

@@ -214,11 +214,8 @@ struct BluesEngine {
     uint64_t box_epoch = 1;   // bumped by every change of the box: cached energies of a State are only good in the box they were computed in
     int batch_R = 1;  // replicas sharing this engine's launches (shapes the launch decomposition in sort_and_tile)
     uint64_t args_epoch = 1;  // bumped whenever a device buffer referenced by the argument records is (re)allocated
-    hipStream_t stream = nullptr, s1 = nullptr, s2 = nullptr, cur = nullptr; bool stream_pooled = false;
+    hipStream_t stream = nullptr, s1 = nullptr, s2 = nullptr, cur = nullptr;   // (stream: from the per-device pool, never destroyed with the engine)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evFork = nullptr, evJ1 = nullptr, evJ2 = nullptr, evA = nullptr, evB = nullptr;
-    hipGraphExec_t gexec = nullptr; int graph_units = 16; bool graph_valid = false, use_graph = false, graph_fork = false;
-    DevCtrl* ctrl_arg = nullptr; DevCtrl host_ctrl;
-    int64_t st_graph_steps = 0;
     // ---- system (host copies, caller order)
     int n = 0;
     double box[3] = {0, 0, 0};
@@ -280,7 +277,7 @@ struct BluesEngine {
     bool k2_dense = false;   // the alchemical kernel's env pairs in their dense form (kernels_alch.h: alchemical_dense_body)
     bool k2_f32 = false;     // ... in fp32 pair arithmetic with the work from per-pair differences (alchemical_dense32_body; round 6)
     int seg_len = 64, waves_tile = 4, wpb = 4, npart = 1;  // K1 decomposition
-    bool fuse_forces = false, fast_step = true, fuse_big = false;  // fuse_big: measured slower (the alchemical role's 140 VGPRs and 36 KB LDS cap the occupancy of the nonbonded role)
+    bool fuse_forces = false, fast_step = true;
     int k1_iw = 64;  // i-atoms per wave in the nonbonded kernel: 64 = classic tile kernel, 8/16 = sub-tile throughput kernel
     int k1_mode = 0;  // 0: tile kernel (lane = i-atom), 1: sub-tile kernel, 2: per-atom Verlet lists + LDS tile image (nonbonded_atom_body), 3: fragment lists (kernels_frag.h), 4: all pairs of a NoCutoff System (kernels_nocutoff.h)
     int pair_mode = 0;   // BLUES_PAIR_*: 1 = the alchemical x environment pairs take the form of kernels_alch.h FORM 1 and are the only nonbonded pairs (NoCutoff)
@@ -324,7 +321,7 @@ struct BluesEngine {
     DBuf<AtomF> d_img_f; DBuf<AtomD> d_img_d;
     DBuf<int> d_sorted_of_orig, d_orig_of_sorted, d_tile_atoms, d_jlist, d_jstage, d_jcount, d_batch_slot, d_ex_start, d_ex_idx, d_islot;
     DBuf<unsigned long long> d_mask_pool;
-    DBuf<DevFlags> d_flags; DBuf<DevAccum> d_acc; DBuf<DevCtrl> d_ctrl; DBuf<double> d_tab_ls, d_tab_le; DBuf<long long> d_stamps;
+    DBuf<DevFlags> d_flags; DBuf<DevAccum> d_acc; DBuf<long long> d_stamps;
     DBuf<double> d_fpart, d_epart_nb, d_fJ, d_self_part, d_e_part, d_fent, d_ftot, d_alch_self, d_epart_b, d_cm_part, d_trace, d_scratch;
     DBuf<int> d_orig_of_islot, d_row_of_orig, d_mobile_atoms, d_mobile_index, d_exc_owner, d_exc_is_env;
     DBuf<double> d_noise; unsigned noise_draw_base = 0; int n_noise = 0; bool noise_valid = false;
@@ -355,9 +352,7 @@ struct BluesEngine {
 
     ~BluesEngine() {
         for (BluesSnapshot* sn : snap_pool) { if (sn->block) hipFree(sn->block); delete sn; }
-        if (gexec) hipGraphExecDestroy(gexec);
         for (hipEvent_t e : {ev0, ev1, evFork, evJ1, evJ2, evA, evB}) if (e) hipEventDestroy(e);
-        if (stream && !stream_pooled) hipStreamDestroy(stream);
         for (hipStream_t q : {s1, s2}) if (q) hipStreamDestroy(q);
     }
 };
@@ -810,7 +805,7 @@ static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
 static int nocut_layout(BluesEngine* h) {
     const int n = h->n;
     h->k1_mode = 4; h->S = 1; h->acap = 0; h->k1_iw = 64; h->seg_len = 64; h->waves_tile = 1; h->npart = 1; h->wpb = 4;
-    h->fuse_forces = false; h->fuse_big = false; h->k2_dense = false; h->k2_f32 = false; h->prune_on = false; h->use_graph = false;
+    h->fuse_forces = false; h->k2_dense = false; h->k2_f32 = false; h->prune_on = false;
     h->skin = h->skin_m = h->trig = 1e30;   // (the step kernels' displacement check never asks for a list)
     h->h_sorted_of_orig.resize(n); h->h_orig_of_sorted.resize(n);
     for (int i = 0; i < n; i++) { h->h_sorted_of_orig[i] = i; h->h_orig_of_sorted[i] = i; }
@@ -887,7 +882,7 @@ static int nocut_layout(BluesEngine* h) {
     } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
     // no frozen-frozen constant: the all-pairs energy kernel has every pair
     h->e_frozen[0] = h->e_frozen[1] = 0.0; h->e_frozen_valid = true;
-    h->sorted_ok = true; h->lists_forced = false; h->pass_valid = false; h->graph_valid = false;
+    h->sorted_ok = true; h->lists_forced = false; h->pass_valid = false;
     h->layout_R = h->batch_R;
     h->args_epoch++;
     return 0;
@@ -1309,7 +1304,7 @@ static int sort_and_tile(BluesEngine* h) {
     } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
     for (int k = 0; k < 3; k++)   // the master positions on the device are the ones just sorted (every caller uploads / downloads first)
         if (hipMemcpy(h->d_x_sort[k].p, h->d_x[k].p, sizeof(double) * n, hipMemcpyDeviceToDevice) != hipSuccess) E_FAIL(h, "hipMemcpy D2D failed");
-    h->sorted_ok = true; h->lists_forced = true; h->pass_valid = false; h->graph_valid = false;
+    h->sorted_ok = true; h->lists_forced = true; h->pass_valid = false;
     h->layout_R = h->batch_R;
     h->args_epoch++;
     std::vector<double>().swap(h->hx);   // (only a layout reads it, and every caller fills it first: 560 KB x 2048 chains of host memory otherwise)
@@ -1346,8 +1341,8 @@ static IntArgs make_int_args(BluesEngine* h) {
     A.prune_trig2 = (float)(h->ptrig * h->ptrig);
     A.total_mass = h->total_mass; A.cm_part = h->d_cm_part.p; A.cm_nblocks = h->int_blocks;
     A.mom_part = h->d_mom_part.p; A.n_mom = h->n_islots / 64 + 2;
-    A.acc = h->d_acc.p; A.work_trace = (h->tracing || h->ctrl_arg) ? h->d_trace.p : nullptr; A.trace_index = h->prog_trace;
-    A.ctrl = h->ctrl_arg; A.stamps = h->d_stamps.p;
+    A.acc = h->d_acc.p; A.work_trace = h->tracing ? h->d_trace.p : nullptr; A.trace_index = h->prog_trace;
+    A.stamps = h->d_stamps.p;
     A.prog = h->prog;
     return A;
 }
@@ -1579,6 +1574,7 @@ template <typename R, bool ENERGY> static int launch_nocut(BluesEngine* h) {
     HIP_OK(h, hipGetLastError());
     return 0;
 }
+
 template <typename R, bool ENERGY> static int launch_nonbonded(BluesEngine* h) {
     if (h->k1_mode == 4) return launch_nocut<R, ENERGY>(h);
     NbArgs<R> a = make_nb_args<R>(h);
@@ -1625,12 +1621,14 @@ template <typename R, bool ENERGY> static int launch_nonbonded(BluesEngine* h) {
     HIP_OK(h, hipGetLastError());
     return 0;
 }
+// the instantiation for the engine's precision (0: fp32 pair math on the fixed-point image)
+static int launch_lists_p(BluesEngine* h, int force, int phase = 0) { return h->precision == 0 ? launch_lists<float>(h, force, phase) : launch_lists<double>(h, force, phase); }
+template <bool ENERGY> static int launch_nonbonded_p(BluesEngine* h) { return h->precision == 0 ? launch_nonbonded<float, ENERGY>(h) : launch_nonbonded<double, ENERGY>(h); }
 
 static AlchArgs make_alch_args(BluesEngine* h, const double ls[3], const double le[3], int slot_mask);
 static AlchDyn make_alch_dyn(const AlchArgs& A) { AlchDyn d; for (int s = 0; s < 3; s++) { d.ls[s] = A.ls[s]; d.le[s] = A.le[s]; } d.slot_mask = A.slot_mask; return d; }
 
-// part (a batch's leader only; kernels_batch.h: k_alchemical_b): 0 every member, 1 those that do not rebuild their lists in this
-// force pass, 2 those that do (both from the work list of the rebuild)
+// part (a batch's leader with a dense alchemical kernel only): 0 both of its kernels; 3 ... 6 one of them, see below
 static int launch_alchemical(BluesEngine* h, const double ls[3], const double le[3], int slot_mask, int part = 0) {
     if (h->alch.empty()) return 0;
     AlchArgs A = make_alch_args(h, ls, le, slot_mask);
@@ -1658,7 +1656,7 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
                 // (part 5 / 6: the dense kernel only, for the members that do not / do rebuild their lists in this pass -- force_pass, fork mode 4)
                 const int* stale = part >= 5 ? h->batch->d_work.p : nullptr;
 #define DENSE32_B(M, NS) do { if (part != 3) hipLaunchKernelGGL((k_alchemical_dense32_b<M>), dim3(nrep), dim3(K2F_THREADS), sizeof(K2FLds<NS>), h->cur, h->batch->d_core.p, D, stale, part == 6 ? 1 : 0); \
-                              if (part < 4) hipLaunchKernelGGL((k_alchemical_b<true, M>), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep, (const int*)nullptr); } while (0)
+                              if (part < 4) hipLaunchKernelGGL((k_alchemical_b<true, M>), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep); } while (0)
                 if (slot_mask == 5) DENSE32_B(5, 2); else if (slot_mask == 2) DENSE32_B(2, 1); else DENSE32_B(-1, 3);
 #undef DENSE32_B
             } else {
@@ -1687,7 +1685,7 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
             const AlchDyn D = make_alch_dyn(A);
             // (part 3: the alchemical x alchemical block only; part 4: the dense kernel only -- force_pass, fork mode 3)
 #define DENSE_B(M) do { if (part != 3) hipLaunchKernelGGL((k_alchemical_dense_b<M>), dim3(nrep), dim3(K2D_THREADS), lds, h->cur, h->batch->d_core.p, D); \
-                        if (part != 4) hipLaunchKernelGGL((k_alchemical_b<true, M>), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep, (const int*)nullptr); } while (0)
+                        if (part != 4) hipLaunchKernelGGL((k_alchemical_b<true, M>), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep); } while (0)
             if (slot_mask == 5) DENSE_B(5); else if (slot_mask == 2) DENSE_B(2); else DENSE_B(-1);
 #undef DENSE_B
         } else {
@@ -1703,10 +1701,9 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
     if (batch_lead(h)) {
         const int nb = std::min(h->k2_nblocks_env, K2_PHYS) + 1, nrep = h->batch->R();   // (a lone chain keeps one block per logical block: shortest chain)
         const AlchDyn D = make_alch_dyn(A);
-        const dim3 g(part == 2 ? std::min(nb * nrep, 8 * REBUILD_GRID) : nb * nrep), b(256);
-        const int* work = h->batch->d_work.p;
-        if (h->pair_mode == BLUES_PAIR_ETHYLENE) {   // (NoCutoff: part is always 0)
-#define ALCH_B1(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M, 1>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep, (const int*)nullptr)
+        const dim3 g(nb * nrep), b(256);
+        if (h->pair_mode == BLUES_PAIR_ETHYLENE) {
+#define ALCH_B1(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M, 1>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep)
             if (fast) { if (slot_mask == 5) ALCH_B1(true, 5); else if (slot_mask == 2) ALCH_B1(true, 2); else ALCH_B1(true, -1); }
             else { if (slot_mask == 5) ALCH_B1(false, 5); else if (slot_mask == 2) ALCH_B1(false, 2); else ALCH_B1(false, -1); }
 #undef ALCH_B1
@@ -1714,8 +1711,7 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
             HIP_OK(h, hipGetLastError());
             return 0;
         }
-#define ALCH_B(F, M) do { if (part == 2) hipLaunchKernelGGL((k_alchemical_stale_b<F, M>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, work); \
-                          else hipLaunchKernelGGL((k_alchemical_b<F, M>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep, part == 1 ? work : (const int*)nullptr); } while (0)
+#define ALCH_B(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep)
         if (fast) { if (slot_mask == 5) ALCH_B(true, 5); else if (slot_mask == 2) ALCH_B(true, 2); else ALCH_B(true, -1); }
         else { if (slot_mask == 5) ALCH_B(false, 5); else if (slot_mask == 2) ALCH_B(false, 2); else ALCH_B(false, -1); }
 #undef ALCH_B
@@ -1745,7 +1741,7 @@ static AlchArgs make_alch_args(BluesEngine* h, const double ls[3], const double 
     A.box = make_box(h); A.rc2 = nocut(h) ? 1e300 : h->cutoff * h->cutoff; A.alpha = h->alpha; A.sc_alpha = h->sc_alpha;
     A.pme = h->nb_method == BLUES_NB_PME_DIRECT; A.annih_elec = h->annih_elec; A.annih_ster = h->annih_ster; A.slot_mask = slot_mask; A.check_env_excl = h->check_env_excl;
     for (int s = 0; s < 3; s++) { A.ls[s] = ls[s]; A.le[s] = le[s]; }
-    A.fJ = h->d_fJ.p; A.self_part = h->d_self_part.p; A.e_part = h->d_e_part.p; A.ctrl = h->ctrl_arg;
+    A.fJ = h->d_fJ.p; A.self_part = h->d_self_part.p; A.e_part = h->d_e_part.p;
     A.img = h->precision == 0 ? h->d_img_f.p : nullptr;
     for (int k = 0; k < 3; k++) A.fscale[k] = (float)(h->box[k] / 4294967296.0);
     return A;
@@ -1761,7 +1757,7 @@ static BondedArgs make_bonded_args(BluesEngine* h) {
     B.box = make_box(h); B.periodic = h->nb_method == BLUES_NB_PME_DIRECT; B.fent = h->d_fent.p; B.n_entries = h->n_entries; B.n = h->n; B.epart = h->d_epart_b.p;
     B.n_mobile = (int)h->mobile.size(); B.n_noise = h->n_noise; B.mobile_atoms = h->d_mobile_atoms.p; B.noise = h->d_noise.p;
     B.n_cent = h->n_cent; B.cent_atoms = h->d_cent_atoms.p; B.cent_params = h->d_cent_params.p;
-    B.seed = h->seed; B.stream = (unsigned)h->replica * 4u; B.draw_base = h->h_draw; B.n_entry_blocks = (h->n_entries + 127) / 128; B.ctrl = h->ctrl_arg;
+    B.seed = h->seed; B.stream = (unsigned)h->replica * 4u; B.draw_base = h->h_draw; B.n_entry_blocks = (h->n_entries + 127) / 128;
     return B;
 }
 
@@ -1791,7 +1787,7 @@ static FinArgs make_fin_args(BluesEngine* h, const double le[3], int slot_mask =
     F.self_part = h->d_self_part.p; F.e_part = h->d_e_part.p; F.jcount_alch = h->d_jcount.p + h->n_lists;
     for (int s = 0; s < 3; s++) F.le[s] = le[s];
     F.slot_mask = slot_mask;
-    F.ftot = h->d_ftot.p; F.alch_self = h->d_alch_self.p; F.acc = h->d_acc.p; F.ctrl = h->ctrl_arg;
+    F.ftot = h->d_ftot.p; F.alch_self = h->d_alch_self.p; F.acc = h->d_acc.p;
     for (int k = 0; k < 3; k++) F.v[k] = h->d_v[k].p;
     F.mass = h->d_mass.p; F.mom_part = h->d_mom_part.p;
     F.frec = h->pme ? h->d_frec.p : nullptr;
@@ -1818,7 +1814,7 @@ static int launch_finalize(BluesEngine* h, const double le[3], int slot_mask = 7
 // program are served by this pass (slots 0 and 2).  What else needs the summed forces resolves the pending sums first.
 // (npart == 1: the per-atom-list kernel's single slab; a lone chain's tile kernel leaves dozens of partial slabs, and four atoms per
 // thread summing them one after the other took longer than k_finalize's thread per atom: 77 against 52 us per step)
-static bool fin_fusable(const BluesEngine* h) { return !nocut(h) && h->fast_step && h->int_blocks == 1 && (h->int_threads == 256 || (h->int_threads == 128 && h->clusters_packed)) && h->npart == 1 && h->n_entries <= STEP_FENT_LDS && h->tune.fuse_finalize != 0 && !h->ctrl_arg; }   // (one slab, the bonded entries fit the step kernel's LDS: step_default_body<CM, true>)
+static bool fin_fusable(const BluesEngine* h) { return !nocut(h) && h->fast_step && h->int_blocks == 1 && (h->int_threads == 256 || (h->int_threads == 128 && h->clusters_packed)) && h->npart == 1 && h->n_entries <= STEP_FENT_LDS && h->tune.fuse_finalize != 0; }   // (one slab, the bonded entries fit the step kernel's LDS: step_default_body<CM, true>)
 static int launch_finalize_deferred(BluesEngine* h, const double le[3], int slot_mask) {
     if (!fin_fusable(h) || (slot_mask & 5) != 5) { h->fin_pending = false; return launch_finalize(h, le, slot_mask); }
     h->fin_pending = true; h->fin_mask = slot_mask;
@@ -1850,33 +1846,6 @@ template <typename R> static int launch_forces_fused(BluesEngine* h, const doubl
     BondedDyn BD; BD.draw_base = B.draw_base; BD.n_entry_blocks = B.n_entry_blocks;
     if (batch_lead(h)) hipLaunchKernelGGL(k_forces_fused_b<R>, dim3(nb1 + nb2 + nb3, h->batch->R()), dim3(256), 0, h->cur, batch_reps_nb<R>(h->batch), h->batch->d_core.p, make_alch_dyn(A), BD, nb1, nb2);
     else if (!batch_dry(h)) hipLaunchKernelGGL(k_forces_fused<R>, dim3(nb1 + nb2 + nb3), dim3(256), 0, h->cur, a, make_nbconst<R>(h), img, A, B, nb1, nb2);
-    h->st_launches++;
-    HIP_OK(h, hipGetLastError());
-    return 0;
-}
-
-static int launch_forces_fused_sub(BluesEngine* h, const double ls[3], const double le[3]) {
-    NbArgs<float> a = make_nb_args<float>(h);
-    AlchArgs A = make_alch_args(h, ls, le, h->pass_fmask);
-    BondedArgs B = make_bonded_args(h);
-    B.n_entry_blocks = (h->n_entries + 255) / 256;
-    const int subs = 64 / h->k1_iw;
-    const int nb1 = (std::max(1, h->n_itiles) * subs * h->waves_tile + 3) / 4;
-    const int nb2 = h->alch.empty() ? 0 : h->k2_nblocks_env + 1;
-    const int nb3 = B.n_entry_blocks + ((int)h->mobile.size() * h->n_noise + 255) / 256;
-    h->noise_draw_base = h->h_draw; h->noise_valid = true;
-    const dim3 grid(nb1 + nb2 + nb3, batch_lead(h) ? h->batch->R() : 1), block(256);
-    if (batch_lead(h)) {
-        BondedDyn BD; BD.draw_base = B.draw_base; BD.n_entry_blocks = B.n_entry_blocks;
-        const AlchDyn AD = make_alch_dyn(A);
-        if (h->k1_iw == 8) hipLaunchKernelGGL(k_forces_fused_sub_b<8>, grid, block, 0, h->cur, h->batch->d_nb_f.p, h->batch->d_core.p, AD, BD, nb1, nb2);
-        else if (h->k1_iw == 16) hipLaunchKernelGGL(k_forces_fused_sub_b<16>, grid, block, 0, h->cur, h->batch->d_nb_f.p, h->batch->d_core.p, AD, BD, nb1, nb2);
-        else hipLaunchKernelGGL(k_forces_fused_sub_b<32>, grid, block, 0, h->cur, h->batch->d_nb_f.p, h->batch->d_core.p, AD, BD, nb1, nb2);
-    } else if (!batch_dry(h)) {
-        if (h->k1_iw == 8) hipLaunchKernelGGL(k_forces_fused_sub<8>, grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p, A, B, nb1, nb2);
-        else if (h->k1_iw == 16) hipLaunchKernelGGL(k_forces_fused_sub<16>, grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p, A, B, nb1, nb2);
-        else hipLaunchKernelGGL(k_forces_fused_sub<32>, grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p, A, B, nb1, nb2);
-    }
     h->st_launches++;
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -2110,12 +2079,13 @@ static int ensure_sorted(BluesEngine* h) {
     return 0;
 }
 
-// side streams and their fork / join events (a batch's leader with the lane-layout alchemical kernel, graph capture); timing events
+// side streams and their fork / join events (force_pass: every forked schedule of a batch's leader, and the fragment-list fork of a
+// lone chain); timing events
 static int ensure_side(BluesEngine* h) {
     if (h->s1) return 0;
     HIP_OK(h, hipStreamCreate(&h->s1));
-    {   // s2 carries a batch's rebuild kernels (force_pass): a few workgroups on the critical path that must find room on CUs the
-        // alchemical kernel has filled -- at equal priority the dispatcher keeps refilling those CUs with that kernel's workgroups
+    {   // s2 carries the dense alchemical kernel of the members that rebuild (force_pass, fork_mode 4): a few workgroups beside the other
+        // members' launch on s1.  That schedule was measured on a stream of the highest priority, which is therefore part of it
         int least = 0, greatest = 0;
         HIP_OK(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
         HIP_OK(h, hipStreamCreateWithPriority(&h->s2, hipStreamDefault, greatest));
@@ -2131,7 +2101,7 @@ static int ensure_timing(BluesEngine* h) {
     return 0;
 }
 
-// one force pass at the current positions: lists (if stale) -> alchemical -> nonbonded -> bonded
+// one force pass at the current positions: lists (if stale) -> alchemical -> nonbonded -> bonded -> the sums
 static int force_pass(BluesEngine* h, int base_L) {
     if (ensure_sorted(h)) return 1;
     double ls[3], le[3];
@@ -2142,53 +2112,45 @@ static int force_pass(BluesEngine* h, int base_L) {
     int fmask = 7;
     if (h->split == "HVRORVH" && h->nprop == 1) fmask = (base_L & 1) ? 5 : 2;
     if (h->split == "L") fmask = 1;   // (the MD leg's one kick per step reads slot 0; no lambda, no other slot)
-    if (h->tune.slot_mask >= 0) fmask = h->tune.slot_mask & 7;
     h->pass_fmask = fmask;
+    // (the fused force kernel, the fused finalize and every periodic form run the bonded entries and the alchemical pairs WITHOUT the custom
+    // forces -- CENT = false, FORM 0: an engine that carries them must be on the decomposed NoCutoff path, where nocut_layout put it)
+    if ((h->n_cent > 0 || h->pair_mode != BLUES_PAIR_STANDARD) && (h->k1_mode != 4 || h->fuse_forces || h->k2_dense))
+        E_FAIL(h, "internal: an engine with custom forces left the decomposed NoCutoff path (k1_mode %d, fuse_forces %d, k2_dense %d)", h->k1_mode, (int)h->fuse_forces, (int)h->k2_dense);
+
+    // ---- which schedule (BluesTuning.fork; every one of them computes the same bits)
+    const int fork_mode = h->batch ? h->batch->tune.fork : h->tune.fork;
+    const bool fused = h->fuse_forces && h->wpb == 4;   // (one launch with the nonbonded, alchemical and bonded roles: nothing to fork)
     // A large batch in per-atom-list mode forks the alchemical kernel onto a side stream after the group lists (which hold its
     // j records): the atoms' own lists are built by a few latency-bound blocks that leave most of the chip idle, and the
-    // alchemical kernel fills it.  Joined before finalize.
-    const int fork_mode = h->batch ? h->batch->tune.fork : h->tune.fork;   // 2: also with the dense alchemical kernel, joined BEFORE the nonbonded kernel
-    const bool fork_env = fork_mode != 0;
-    const bool decomposed = !(h->fuse_forces && h->wpb == 4) && !(h->k1_mode == 1 && h->precision == 0 && h->fuse_big);
-    // (round 3 kept the dense alchemical kernel off the side stream: a 512-thread workgroup with ~137 KB of LDS per chain cannot share a
-    // CU with the nonbonded kernel's, and beside the rebuild's small workgroups it ran at half speed: 516 us per step with every kernel
-    // alone against 540)
-    const bool fork = fork_env && decomposed && batch_lead(h) && h->k1_mode == 2 && !h->alch.empty() && !h->ctrl_arg;
+    // alchemical kernel fills it.  Joined before finalize (fork_mode 2: before the nonbonded kernel).
+    const bool fork = fork_mode != 0 && !fused && batch_lead(h) && h->k1_mode == 2 && !h->alch.empty();
+    const bool beside_lists = fork && fork_mode == 4 && h->k2_dense && h->k2_f32;
     // with the dense alchemical kernel only the two SMALL kernels of a pass go to the side stream (alchemical x alchemical block,
     // bonded entries + the next step's noise: 54 us per 1024 chains, 168 / 70 registers, 37 KB / no LDS) -- they run beside the
     // builder of the atoms' lists (85 us, no LDS, 94 registers) and are done before it: 756 -> 716 us per step of 1024 chains.
-    // The dense kernel itself beside that builder (fork = 2) gains nothing; beside the GROUP-list builder the small kernels cost
+    // The dense kernel itself beside that builder (fork_mode 2) gains nothing; beside the GROUP-list builder the small kernels cost
     // it what they saved (round 4, first half).
-    // 4 (round 6): the work list and the group lists are two latency-bound kernels of a few hundred workgroups -- 68 us during which the
-    // chip idles.  The kernels that need nothing from them start WITH them on the side streams: the two small ones at once, the dense
-    // alchemical kernel of the members that do not rebuild as soon as the work list says who they are (all but ~40 of 1024), that of the
-    // members that rebuild behind the group lists; all joined before the nonbonded kernel, which keeps the device to itself.
-    const bool beside_lists = fork && fork_mode == 4 && h->k2_dense && h->k2_f32;
+    // (round 3 kept the dense alchemical kernel off the side stream: a 512-thread workgroup with ~137 KB of LDS per chain cannot share a
+    // CU with the nonbonded kernel's, and beside the rebuild's small workgroups it ran at half speed: 516 us per step with every kernel
+    // alone against 540)
     const bool small_side = fork && h->k2_dense && fork_mode != 2 && fork_mode != 3 && !beside_lists;   // (3: every alchemical kernel and the bonded entries on the side stream, joined before the sums)
-    if (fork && ensure_side(h)) return 1;
-    // k2_early (off by default): the alchemical kernel of the members that do NOT rebuild needs nothing from the rebuild and can
-    // start as soon as the work list says who they are, with the rebuild kernels on a high-priority stream beside it and the
-    // members that rebuild following their group lists.  Measured at R = 512 (round 3): 545-565 us per step against 545-555
-    // without -- the step is bound by the sum of the kernels' work, not by their order ("what the timeline says").
-    // In the default order the atoms' lists are enqueued BEFORE the alchemical kernel: behind its 12,800 small workgroups the
-    // few workgroups of the rebuild waited for room on full CUs (245 us against 107 us alone).
-    const bool early = fork && h->s2 && !h->k2_dense && !h->lists_forced && !h->tune.force_lists && (h->batch ? h->batch->tune.k2_early : h->tune.k2_early) != 0;
-    int rc = 0;
-    bool wait_lists = false;
     // fragment lists (k1_mode 3) in a batch: the alchemical kernel and the bonded entries (+ the next O step's noise) need the
     // alchemical tile's list only -- they run on the side stream beside the fragment-list kernels (a rebuild or a prune of one or two
     // members: a few latency-bound workgroups) and the head of the nonbonded kernel, joined before the sums
     // (a lone chain of a few thousand fragments too: its step is eight launches back to back, and the alchemical tile's list, the
     // alchemical kernel and the bonded entries -- a third of them -- need nothing from the fragment lists)
-    const bool fork3 = fork_env && h->k1_mode == 3 && !h->ctrl_arg && (batch_lead(h) || (!batch_dry(h) && h->frag_NI >= 2048));
-    if (fork3) {
-        if (ensure_side(h)) return 1;
-        hipStream_t main_stream = h->cur;
+    const bool fork3 = fork_mode != 0 && h->k1_mode == 3 && (batch_lead(h) || (!batch_dry(h) && h->frag_NI >= 2048));
+    if ((fork || fork3) && ensure_side(h)) return 1;
+    hipStream_t main_stream = h->cur;
+    int rc = 0;
+
+    if (fork3) {   // ---- fragment lists, forked (k1_mode 3 is mixed precision only: the _p launches below are the <float> ones)
         HIP_OK(h, hipEventRecord(h->evFork, main_stream)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evFork, 0));
         // (the alchemical tile's list -- work list + builder, 6 + 22 us at R = 16 -- is read by the side stream's kernels only; the list
         // kernels read the flags, nobody writes them before the nonbonded kernel: it goes to the side stream with its readers)
         // (both of its kernels read the flags the nonbonded kernel resets: that kernel waits for evA)
-        h->cur = h->s1; rc = launch_lists<float>(h, h->lists_forced, 1); h->cur = main_stream;
+        h->cur = h->s1; rc = launch_lists_p(h, h->lists_forced, 1); h->cur = main_stream;
         if (rc) return 1;
         HIP_OK(h, hipEventRecord(h->evA, h->s1));
         // (the DENSE alchemical kernel -- a 512-thread workgroup with ~158 KB of LDS per chain -- stays on the main stream, behind the
@@ -2200,92 +2162,64 @@ static int force_pass(BluesEngine* h, int base_L) {
         // (tried and dropped in round 5: the nonbonded kernel in two launches -- the members whose lists are current on the main stream
         // beside the rebuild / prune of the others on a second side stream, those members' share behind it: 707 against 552 us per
         // step at R = 16, 2,355 against 2,020 at R = 64; the list kernels' workgroups slow the force kernel's more than they hide)
-        rc = launch_lists<float>(h, h->lists_forced, 5);
-        if (rc) return 1;
+        if (launch_lists_p(h, h->lists_forced, 5)) return 1;
         h->lists_forced = false;
         HIP_OK(h, hipStreamWaitEvent(main_stream, h->evA, 0));
-        if (launch_nonbonded<float, false>(h)) return 1;
+        if (launch_nonbonded_p<false>(h)) return 1;
         if (h->k2_dense && launch_alchemical(h, ls, le, fmask, 4)) return 1;
         if (launch_pme(h, 0)) return 1;
-        HIP_OK(h, hipStreamWaitEvent(h->cur, h->evJ1, 0));
-        if (launch_finalize_deferred(h, le, fmask)) return 1;
-        h->pass_valid = true; h->pass_L = base_L; h->st_passes++; h->vel_clean = true; h->acc_cache_valid = false;
-        HIP_OK(h, hipGetLastError());
-        return 0;
-    }
-    if (beside_lists) {
-        hipStream_t main_stream = h->cur;
-#define LISTS(ph) (h->precision == 0 ? launch_lists<float>(h, h->lists_forced, ph) : launch_lists<double>(h, h->lists_forced, ph))
+        HIP_OK(h, hipStreamWaitEvent(main_stream, h->evJ1, 0));
+    } else if (beside_lists) {   // ---- fork_mode 4 (round 6), beside the lists
+        // the work list and the group lists are two latency-bound kernels of a few hundred workgroups -- 68 us during which the chip
+        // idles.  The kernels that need nothing from them start WITH them on the side streams: the two small ones at once, the dense
+        // alchemical kernel of the members that do not rebuild as soon as the work list says who they are (all but ~40 of 1024), that of the
+        // members that rebuild behind the group lists; all joined before the nonbonded kernel, which keeps the device to itself.
         HIP_OK(h, hipEventRecord(h->evFork, main_stream)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evFork, 0));
         h->cur = h->s1; rc = launch_alchemical(h, ls, le, fmask, 3) || launch_bonded(h, true); h->cur = main_stream;
         if (rc) return 1;
-        if (LISTS(3)) return 1;
+        if (launch_lists_p(h, h->lists_forced, 3)) return 1;
         HIP_OK(h, hipEventRecord(h->evA, main_stream)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evA, 0));
         h->cur = h->s1; rc = launch_alchemical(h, ls, le, fmask, 5); h->cur = main_stream;
         if (rc) return 1;
         HIP_OK(h, hipEventRecord(h->evJ1, h->s1));
-        if (LISTS(4)) return 1;
+        if (launch_lists_p(h, h->lists_forced, 4)) return 1;
         HIP_OK(h, hipEventRecord(h->evJ2, main_stream)); HIP_OK(h, hipStreamWaitEvent(h->s2, h->evJ2, 0));
         h->cur = h->s2; rc = launch_alchemical(h, ls, le, fmask, 6); h->cur = main_stream;
         if (rc) return 1;
         HIP_OK(h, hipEventRecord(h->evB, h->s2));
-        if (LISTS(2)) return 1;
-#undef LISTS
+        if (launch_lists_p(h, h->lists_forced, 2)) return 1;
         HIP_OK(h, hipStreamWaitEvent(main_stream, h->evJ1, 0)); HIP_OK(h, hipStreamWaitEvent(main_stream, h->evB, 0));
-    } else if (fork) {
-        hipStream_t main_stream = h->cur;
-        hipStream_t rb = early ? h->s2 : main_stream;   // the rebuild's stream (high priority: see engine creation)
-#define LISTS(ph) (h->precision == 0 ? launch_lists<float>(h, h->lists_forced, ph) : launch_lists<double>(h, h->lists_forced, ph))
-        if (early) { HIP_OK(h, hipEventRecord(h->evFork, main_stream)); HIP_OK(h, hipStreamWaitEvent(rb, h->evFork, 0)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evFork, 0)); }
-        h->cur = rb; rc = LISTS(3); h->cur = main_stream;
-        if (rc) return 1;
-        if (early) {
-            HIP_OK(h, hipEventRecord(h->evA, rb)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evA, 0));
-            h->cur = h->s1; rc = launch_alchemical(h, ls, le, fmask, 1); h->cur = main_stream;
-            if (rc) return 1;
-        }
-        h->cur = rb; rc = LISTS(4); h->cur = main_stream;
-        if (rc) return 1;
-        HIP_OK(h, hipEventRecord(h->evJ2, rb)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evJ2, 0));
-        h->cur = rb; rc = LISTS(2); h->cur = main_stream;
-        if (rc) return 1;
-        if (early) { HIP_OK(h, hipEventRecord(h->evB, rb)); wait_lists = true; }
-#undef LISTS
-        h->cur = h->s1; rc = launch_alchemical(h, ls, le, fmask, small_side ? 3 : (early ? 2 : 0)) || launch_bonded(h, true); h->cur = main_stream;   // (bonded terms and the next O step's noise need no list either)
+        h->lists_forced = false;
+        if (launch_nonbonded_p<false>(h)) return 1;
+        if (launch_pme(h, 0)) return 1;
+        HIP_OK(h, hipStreamWaitEvent(main_stream, h->evJ1, 0));
+    } else if (fork) {   // ---- forked
+        // (the atoms' lists are enqueued BEFORE the alchemical kernel: behind its 12,800 small workgroups the few workgroups of the
+        // rebuild waited for room on full CUs -- 245 us against 107 us alone)
+        if (launch_lists_p(h, h->lists_forced, 3) || launch_lists_p(h, h->lists_forced, 4)) return 1;
+        HIP_OK(h, hipEventRecord(h->evJ2, main_stream)); HIP_OK(h, hipStreamWaitEvent(h->s1, h->evJ2, 0));
+        if (launch_lists_p(h, h->lists_forced, 2)) return 1;
+        h->cur = h->s1; rc = launch_alchemical(h, ls, le, fmask, small_side ? 3 : 0) || launch_bonded(h, true); h->cur = main_stream;   // (bonded terms and the next O step's noise need no list either)
         if (rc) return 1;
         HIP_OK(h, hipEventRecord(h->evJ1, h->s1));
         if (small_side && launch_alchemical(h, ls, le, fmask, 4)) return 1;   // (the dense kernel follows the atoms' lists on the main stream)
-        if (wait_lists) HIP_OK(h, hipStreamWaitEvent(main_stream, h->evB, 0));
-    } else {
-        rc = h->precision == 0 ? launch_lists<float>(h, h->lists_forced, 0) : launch_lists<double>(h, h->lists_forced, 0);
-        if (rc) return 1;
-    }
-    h->lists_forced = false;
-    // (the fused force kernels, the fused finalize and every periodic form run the bonded entries and the alchemical pairs WITHOUT the custom
-    // forces -- CENT = false, FORM 0: an engine that carries them must be on the decomposed NoCutoff path, where nocut_layout put it)
-    if ((h->n_cent > 0 || h->pair_mode != BLUES_PAIR_STANDARD) && (h->k1_mode != 4 || h->fuse_forces || h->fuse_big || h->k2_dense || h->use_graph))
-        E_FAIL(h, "internal: an engine with custom forces left the decomposed NoCutoff path (k1_mode %d, fuse_forces %d, fuse_big %d, k2_dense %d)", h->k1_mode, (int)h->fuse_forces, (int)h->fuse_big, (int)h->k2_dense);
-    if (h->fuse_forces && h->wpb == 4) {
-        rc = h->precision == 0 ? launch_forces_fused<float>(h, ls, le) : launch_forces_fused<double>(h, ls, le);
-        if (rc) return 1;
+        h->lists_forced = false;
+        if (fork_mode == 2) HIP_OK(h, hipStreamWaitEvent(main_stream, h->evJ1, 0));   // (the nonbonded kernel has the device to itself)
+        if (launch_nonbonded_p<false>(h)) return 1;
         if (launch_pme(h, 0)) return 1;
-        if (launch_finalize_deferred(h, le, fmask)) return 1;
-    } else if (h->k1_mode == 1 && h->precision == 0 && h->fuse_big) {
-        if (launch_forces_fused_sub(h, ls, le)) return 1;
-        if (launch_pme(h, 0)) return 1;
-        if (launch_finalize(h, le, fmask)) return 1;
-    } else {
-        // (the alchemical x alchemical block stays a launch of its own on the main stream: in the bonded entries' grid it took 49 us against
-        // 18 + 13; on a side stream beside the list rebuild, with the bonded entries, the step stayed at 419 us -- the two small kernels
+        HIP_OK(h, hipStreamWaitEvent(main_stream, h->evJ1, 0));
+    } else {   // ---- serial: one stream
+        if (launch_lists_p(h, h->lists_forced)) return 1;
+        h->lists_forced = false;
+        // (decomposed, the alchemical x alchemical block stays a launch of its own on the main stream: in the bonded entries' grid it took 49 us
+        // against 18 + 13; on a side stream beside the list rebuild, with the bonded entries, the step stayed at 419 us -- the two small kernels
         // overlapped, the group-list builder they ran beside went from 47 to 62 us)
-        if (!fork && launch_alchemical(h, ls, le, fmask)) return 1;
-        if (fork && fork_mode == 2) HIP_OK(h, hipStreamWaitEvent(h->cur, h->evJ1, 0));   // (the nonbonded kernel has the device to itself)
-        rc = h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h);
-        if (rc) return 1;
-        if (launch_pme(h, 0)) return 1;
-        if (fork) { HIP_OK(h, hipStreamWaitEvent(h->cur, h->evJ1, 0)); if (launch_finalize_deferred(h, le, fmask)) return 1; }
-        else { if (launch_bonded(h, true)) return 1; if (launch_finalize_deferred(h, le, fmask)) return 1; }
+        if (fused) rc = h->precision == 0 ? launch_forces_fused<float>(h, ls, le) : launch_forces_fused<double>(h, ls, le);
+        else rc = launch_alchemical(h, ls, le, fmask) || launch_nonbonded_p<false>(h);
+        if (rc || launch_pme(h, 0)) return 1;
+        if (!fused && launch_bonded(h, true)) return 1;
     }
+    if (launch_finalize_deferred(h, le, fmask)) return 1;
     h->pass_valid = true; h->pass_L = base_L; h->st_passes++; h->vel_clean = true; h->acc_cache_valid = false;
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -2398,12 +2332,12 @@ static int energy_launch(BluesEngine* h) {
     // what _computeAlchemicalCorrection and _syncStatesMDtoNCMC ask for next (reference blues/simulation.py:1100-1119),
     // and only the alchemical terms differ -- it comes out of the same pass (energy_sum) instead of a second full evaluation
     double ls[3] = {h->cur_ls, 1.0, h->cur_ls}, le[3] = {h->cur_le, 1.0, h->cur_le};
-    int rc = h->precision == 0 ? launch_lists<float>(h, h->lists_forced) : launch_lists<double>(h, h->lists_forced);
+    int rc = launch_lists_p(h, h->lists_forced);
     h->lists_forced = false;
     if (rc) return 1;
     h->pass_valid = false;  // slabs are about to be overwritten with parameters that are not a regular pass
     if (launch_alchemical(h, ls, le, 1)) return 1;
-    rc = h->precision == 0 ? launch_nonbonded<float, true>(h) : launch_nonbonded<double, true>(h);
+    rc = launch_nonbonded_p<true>(h);
     if (rc) return 1;
     if (launch_pme(h, 1)) return 1;
     const EnergyShape g = energy_shape(h);
@@ -2647,99 +2581,6 @@ static int switching_close(BluesEngine* h) {
     return 0;
 }
 
-// ---- hipGraph path for the steady state of "H V R O R V H" (nprop = 1): one unit = [integrate | lists |
-// (alchemical || nonbonded || bonded+noise) | finalize]; the three force kernels are forked onto side streams
-// so they overlap, and launch gaps shrink to in-graph dependencies.  Step-dependent values come from DevCtrl.
-static std::vector<Program> steady_programs(const BluesEngine* h) {
-    std::vector<Program> out;
-    Program p; p.n = 0;
-    auto add = [&](int op) { p.ops[p.n++] = (unsigned char)op; };
-    add(OP_V0); add(OP_H01); add(OP_END);
-    if (h->remove_cm) {
-        if (h->int_blocks == 1) add(OP_CM_BLOCK);
-        else { add(OP_CM_REDUCE); out.push_back(p); p.n = 0; add(OP_CM_APPLY); }
-    }
-    add(OP_H12); add(OP_V2); add(OP_R); add(OP_O); add(OP_R);
-    out.push_back(p);
-    return out;
-}
-
-static int capture_graph(BluesEngine* h) {
-    if (h->gexec) { hipGraphExecDestroy(h->gexec); h->gexec = nullptr; }
-    h->graph_valid = false;
-    const Program saved = h->prog; const int saved_trace = h->prog_trace; const unsigned saved_base = h->prog_draw_base;
-    const bool saved_nv = h->noise_valid; const unsigned saved_nb = h->noise_draw_base;
-    const int64_t saved_launches = h->st_launches;
-    h->ctrl_arg = h->d_ctrl.p;
-    const std::vector<Program> progs = steady_programs(h);
-    const double dummy[3] = {1.0, 1.0, 1.0};
-    int rc = 0;
-    hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) { h->ctrl_arg = nullptr; E_FAIL(h, "hipStreamBeginCapture: %s", hipGetErrorString(e)); }
-    for (int u = 0; u < h->graph_units && !rc; u++) {
-        h->cur = h->stream;
-        for (const Program& p : progs) {
-            h->prog = p;
-            IntArgs A = make_int_args(h);
-            hipLaunchKernelGGL(k_integrate, dim3(h->int_blocks), dim3(h->int_threads), 0, h->cur, A);
-        }
-        rc |= h->precision == 0 ? launch_lists<float>(h, 0) : launch_lists<double>(h, 0);
-        if (h->graph_fork) {
-            rc |= ensure_side(h);
-            rc |= hipEventRecord(h->evFork, h->stream) != hipSuccess;
-            rc |= hipStreamWaitEvent(h->s1, h->evFork, 0) != hipSuccess;
-            rc |= hipStreamWaitEvent(h->s2, h->evFork, 0) != hipSuccess;
-            h->cur = h->s1; rc |= launch_alchemical(h, dummy, dummy, 7);
-            h->cur = h->s2; rc |= launch_bonded(h, true);
-            h->cur = h->stream; rc |= h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h);
-            rc |= hipEventRecord(h->evJ1, h->s1) != hipSuccess;
-            rc |= hipEventRecord(h->evJ2, h->s2) != hipSuccess;
-            rc |= hipStreamWaitEvent(h->stream, h->evJ1, 0) != hipSuccess;
-            rc |= hipStreamWaitEvent(h->stream, h->evJ2, 0) != hipSuccess;
-        } else {
-            rc |= launch_alchemical(h, dummy, dummy, 7);
-            rc |= h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h);
-            rc |= launch_bonded(h, true);
-        }
-        rc |= launch_finalize(h, dummy);
-    }
-    hipGraph_t graph = nullptr;
-    e = hipStreamEndCapture(h->stream, &graph);
-    h->cur = h->stream; h->ctrl_arg = nullptr;
-    h->prog = saved; h->prog_trace = saved_trace; h->prog_draw_base = saved_base; h->noise_valid = saved_nv; h->noise_draw_base = saved_nb;
-    h->st_launches = saved_launches;
-    if (rc || e != hipSuccess || !graph) { if (graph) hipGraphDestroy(graph); E_FAIL(h, "graph capture failed: %s", hipGetErrorString(e)); }
-    e = hipGraphInstantiate(&h->gexec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (e != hipSuccess) { h->gexec = nullptr; E_FAIL(h, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-    h->graph_valid = true;
-    return 0;
-}
-
-// returns the number of whole steps advanced through graph replays (0 if the state is not the steady state)
-static int try_graph_steps(BluesEngine* h, int max_steps) {
-    if (!h->use_graph || h->split != "HVRORVH" || h->nprop != 1) return 0;
-    if (h->h_step < 1 || !h->pass_valid || h->x_edited || h->h_first_step < 1) return 0;
-    if (h->prog.n != 3 || h->prog.ops[0] != OP_V0 || h->prog.ops[1] != OP_H01 || h->prog.ops[2] != OP_END) return 0;
-    if (h->pass_L != 2 * h->h_step - 1 || h->h_lambda_step != 2 * h->h_step || h->lists_forced) return 0;
-    int count = std::min(max_steps, h->nsteps - h->h_step);
-    count -= count % h->graph_units;
-    if (count <= 0) return 0;
-    if (!h->graph_valid && capture_graph(h)) return -1;
-    DevCtrl& c = h->host_ctrl;
-    c.kint = 0; c.kpass = 0; c.L0 = h->pass_L; c.draw0 = h->h_draw; c.trace0 = h->prog_trace; c.n_lambda = h->n_lambda;
-    c.tab_ls = h->d_tab_ls.p; c.tab_le = h->d_tab_le.p;
-    if (hipMemcpyAsync(h->d_ctrl.p, &c, sizeof c, hipMemcpyHostToDevice, h->stream) != hipSuccess) { h->err = "ctrl upload failed"; return -1; }
-    for (int r = 0; r < count / h->graph_units; r++)
-        if (hipGraphLaunch(h->gexec, h->stream) != hipSuccess) { h->err = "hipGraphLaunch failed"; return -1; }
-    h->h_step += count; h->steps_since_sort += count; h->h_lambda_step += 2 * count; h->h_lambda = (double)h->h_lambda_step / h->n_lambda;
-    h->cur_ls = h->tab_ls[h->h_lambda_step]; h->cur_le = h->tab_le[h->h_lambda_step];
-    h->h_draw += (unsigned)count; h->pass_L += 2 * count;
-    h->prog_trace = h->h_step - 1; h->prog_draw_base = h->h_draw; h->noise_draw_base = h->h_draw; h->noise_valid = true;
-    h->st_passes += count; h->st_launches += (int64_t)count * 6; h->st_graph_steps += count;
-    return count;
-}
-
 // reference blues/integrators.py:159-209
 // One NCMC step = head (everything that may differ between the replicas of a batch: the first-step block and the
 // work of an instantaneous Move, which needs a synchronous total energy) + body (the splitting passes; identical
@@ -2796,11 +2637,6 @@ static int step_body(BluesEngine* h) {
 static int do_steps(BluesEngine* h, int nsteps) {
     if (ensure_sorted(h)) return 1;
     for (int s = 0; s < nsteps; s++) {
-        {
-            const int adv = try_graph_steps(h, nsteps - s);
-            if (adv < 0) return 1;
-            if (adv > 0) { s += adv - 1; continue; }
-        }
         if (!nocut(h) && h->h_step > 0 && h->h_step % RESORT_POLL == 0 && poll_resort(h)) return 1;   // (NoCutoff: no lists, nothing to poll)
         if (step_head(h)) return 1;
         if (step_body(h)) return 1;
@@ -2860,7 +2696,7 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
 #define BC(f) if (a->f != b->f) { *why = #f; return false; }
     BC(device) BC(n) BC(precision) BC(nsteps) BC(nprop) BC(n_lambda) BC(split) BC(remove_cm) BC(dt) BC(gamma) BC(kT) BC(tol) BC(prop_min) BC(prop_max)
     BC(n_itiles) BC(n_tiles) BC(jcap) BC(n_islots) BC(pool_cap) BC(PA) BC(k2_nblocks_env) BC(k2_jiter) BC(seg_len) BC(waves_tile) BC(wpb) BC(npart)
-    BC(fuse_forces) BC(fast_step) BC(fuse_big) BC(k2_dense) BC(k2_f32) BC(k1_iw) BC(k1_mode) BC(acap) BC(S) BC(n_lists) BC(n_entries) BC(int_blocks) BC(int_threads) BC(clusters_packed) BC(n_noise) BC(n_rows)
+    BC(fuse_forces) BC(fast_step) BC(k2_dense) BC(k2_f32) BC(k1_iw) BC(k1_mode) BC(acap) BC(S) BC(n_lists) BC(n_entries) BC(int_blocks) BC(int_threads) BC(clusters_packed) BC(n_noise) BC(n_rows)
     BC(frag_F) BC(frag_NI) BC(frag_nblk) BC(frag_fpw) BC(frag_nwg) BC(frag_rel)
     BC(cutoff) BC(alpha) BC(sc_alpha) BC(annih_elec) BC(annih_ster) BC(nb_method) BC(pme) BC(pme_K[0]) BC(pme_K[1]) BC(pme_K[2]) BC(pme_order) BC(restr_k) BC(total_mass)
     // (not the box: a MonteCarloBarostat leaves every member in its own; margins, fixed-point scales and PME tables are per member in the records)
@@ -3264,7 +3100,7 @@ void blues_tuning_default(BluesTuning* t) {
     memset(t, 0, sizeof *t);
     t->struct_size = (int32_t)sizeof *t;
     t->prune_margin = -1.0;
-    t->k1_mode = -1; t->fuse_forces = -1; t->fuse_big = -1; t->fast_step = -1; t->slot_mask = -1; t->fork = 1; t->k2_dense = -1; t->use_graph = -1; t->graph_fork = -1; t->fuse_finalize = 1;
+    t->k1_mode = -1; t->fuse_forces = -1; t->fast_step = -1; t->fork = 1; t->k2_dense = -1; t->fuse_finalize = 1;
 }
 int blues_set_tuning(const BluesTuning* t) {
     if (!t) { blues_tuning_default(&g_tuning); return 0; }
@@ -3390,24 +3226,16 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
       static std::mutex pool_mu; static std::map<int, std::vector<hipStream_t>> pool; static std::map<int, size_t> next;
       std::lock_guard<std::mutex> lk(pool_mu);
       std::vector<hipStream_t>& v = pool[h->device];
-      if (h->tune.use_graph > 0) { HIP_OK(h, hipStreamCreate(&h->stream)); h->stream_pooled = false; }   // (a stream under graph capture must see no other engine's work)
-      else {
-          if (v.size() < 8) { hipStream_t q = nullptr; HIP_OK(h, hipStreamCreate(&q)); v.push_back(q); h->stream = q; }
-          else h->stream = v[next[h->device]++ % v.size()];
-          h->stream_pooled = true;
-      }
+      if (v.size() < 8) { hipStream_t q = nullptr; HIP_OK(h, hipStreamCreate(&q)); v.push_back(q); h->stream = q; }
+      else h->stream = v[next[h->device]++ % v.size()];
     }
     h->cur = h->stream;
-    if (h->tune.use_graph >= 0) h->use_graph = h->tune.use_graph != 0;
     if (h->tune.fast_step >= 0) h->fast_step = h->tune.fast_step != 0;
-    if (h->tune.fuse_big >= 0) h->fuse_big = h->tune.fuse_big != 0;
-    if (h->tune.graph_units > 0) h->graph_units = h->tune.graph_units;
-    if (h->tune.graph_fork >= 0) h->graph_fork = h->tune.graph_fork != 0;
     try {
         for (int k = 0; k < 3; k++) { h->d_x[k].alloc(n); h->d_v[k].alloc(n); h->d_xbuild[k].alloc(n); h->d_x_sort[k].alloc(n); }
         h->d_stage.alloc((size_t)3 * n); h->d_xfer_out.alloc(4);
         h->d_mass.upload(h->T->mass); h->d_charge.upload(h->T->charge); h->d_sigma.upload(h->T->sigma); h->d_eps.upload(h->T->eps);
-        h->d_flags.alloc(1); h->d_acc.alloc(1); h->d_ctrl.alloc(1); h->d_stamps.alloc(64); h->d_tab_ls.upload(h->tab_ls); h->d_tab_le.upload(h->tab_le); h->d_ftot.alloc((size_t)9 * n); h->d_alch_self.alloc(9 * 64);
+        h->d_flags.alloc(1); h->d_acc.alloc(1); h->d_stamps.alloc(64); h->d_ftot.alloc((size_t)9 * n); h->d_alch_self.alloc(9 * 64);
         h->d_alch_orig.upload(h->alch); h->d_alch_local.upload(h->T->alch_local);
         // (the protocol-work trace: one slot per step of the switch; an MD integrator has no H step, no protocol work -- and an
         // nsteps of 2^30, which used to be 8 GiB of HBM per MD engine)
@@ -3551,7 +3379,7 @@ static int reshape_groups(BluesEngine* h, int S, int cap) {
     h->n_lists = (std::max(1, h->n_itiles) + S - 1) / S;
     h->n_tiles = h->n_lists + (h->alch.empty() ? 0 : 1);
     h->pool_cap = std::max(1, h->n_tiles) * MASK_QUOTA;
-    h->lists_forced = true; h->pass_valid = false; h->graph_valid = false;
+    h->lists_forced = true; h->pass_valid = false;
     h->args_epoch++;
     h->st_reshapes++;
     return 0;
@@ -3822,12 +3650,12 @@ int blues_get_forces(BluesEngine* h, double* out, int32_t n_atoms) {
     // forces at the current alchemical parameters: evaluate a pass whose slot 0 carries them
     if (ensure_sorted(h)) return 1;
     double ls[3] = {h->cur_ls, h->cur_ls, h->cur_ls}, le[3] = {h->cur_le, h->cur_le, h->cur_le};
-    int rc = h->precision == 0 ? launch_lists<float>(h, h->lists_forced) : launch_lists<double>(h, h->lists_forced);
+    int rc = launch_lists_p(h, h->lists_forced);
     h->lists_forced = false;
     if (rc) return 1;
     h->pass_valid = false;
     if (launch_alchemical(h, ls, le, 1)) return 1;
-    rc = h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h);
+    rc = launch_nonbonded_p<false>(h);
     if (rc) return 1;
     if (launch_pme(h, 0)) return 1;
     if (launch_bonded_and_finalize(h, le, false)) return 1;
@@ -4042,16 +3870,16 @@ int blues_time_nonbonded(BluesEngine* h, int32_t reps, double* usec) {
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
     if (ensure_sorted(h)) return 1;
-    int rc = h->precision == 0 ? launch_lists<float>(h, 1) : launch_lists<double>(h, 1);
+    int rc = launch_lists_p(h, 1);
     if (rc) return 1;
     h->pass_valid = false;
     // (with pruned lists: the first launch prunes, the acknowledged state is what the timed launches see -- the steady state
     // between two prunes; blues_batch_time_nonbonded_modes times both kinds of pass)
-    for (int w = 0; w < 3; w++) { rc = h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h); if (rc) return 1; }
+    for (int w = 0; w < 3; w++) { rc = launch_nonbonded_p<false>(h); if (rc) return 1; }
     if (h->prune_on && h->k1_mode == 2) hipLaunchKernelGGL(k_prune_set, dim3(1), dim3(256), 0, h->stream, (const RepCore*)nullptr, h->d_pneed.p, h->n_islots, 0);
     if (ensure_timing(h)) return 1;
     HIP_OK(h, hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps; r++) { rc = h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h); if (rc) return 1; }
+    for (int r = 0; r < reps; r++) { rc = launch_nonbonded_p<false>(h); if (rc) return 1; }
     HIP_OK(h, hipEventRecord(h->ev1, h->stream));
     HIP_OK(h, hipEventSynchronize(h->ev1));
     float ms = 0.f;
@@ -4098,11 +3926,11 @@ int blues_time_list_build(BluesEngine* h, int32_t reps, double* usec) {
     if (flush_program(h)) return 1;
     if (ensure_sorted(h)) return 1;
     int rc = 0;
-    for (int w = 0; w < 2 && !rc; w++) rc = h->precision == 0 ? launch_lists<float>(h, 1) : launch_lists<double>(h, 1);
+    for (int w = 0; w < 2 && !rc; w++) rc = launch_lists_p(h, 1);
     if (rc) return 1;
     if (ensure_timing(h)) return 1;
     HIP_OK(h, hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps && !rc; r++) rc = h->precision == 0 ? launch_lists<float>(h, 1) : launch_lists<double>(h, 1);
+    for (int r = 0; r < reps && !rc; r++) rc = launch_lists_p(h, 1);
     if (rc) return 1;
     HIP_OK(h, hipEventRecord(h->ev1, h->stream));
     HIP_OK(h, hipEventSynchronize(h->ev1));
@@ -4384,7 +4212,6 @@ int blues_batch_create(BluesEngine* const* engines, int32_t count, BluesBatch** 
         if (flush_program(m) || hipStreamSynchronize(m->stream) != hipSuccess) { g_batch_create_error = "could not drain engine stream: " + m->err; batch_detach_all(B); delete B; return 1; }
         B->eng.push_back(m); m->batch = B; m->batch_index = r;
         m->batch_R = std::max((int)count, m->tune.assume_batch);   // (assume_batch: a floor, so that small test batches take the large-batch decomposition too)
-        m->use_graph = false;  // graph replays carry per-engine frozen arguments
     }
     if (batch_plan_shape(B, true)) { g_batch_create_error = B->err; batch_detach_all(B); delete B; return 1; }
     if (engines[0]->sorted_ok && engines[0]->k1_mode != 2 && engines[0]->k1_mode != 3)
@@ -4788,13 +4615,13 @@ int blues_batch_time_nonbonded_modes(BluesBatch* b, int32_t reps, double usec[2]
     b->leader = h; b->lockstep = true;
     const bool dual = h->prune_on && h->k1_mode == 2;
     if (ensure_timing(h)) { b->err = h->err; batch_leave(b); return 1; }
-    int rc = h->precision == 0 ? launch_lists<float>(h, 1) : launch_lists<double>(h, 1);
+    int rc = launch_lists_p(h, 1);
     float ms[2] = {0.f, 0.f};
     for (int mode = 0; mode < 2 && !rc; mode++) {   // 0: pruned lists current, 1: stale (every launch prunes)
-        for (int w = 0; w < 3 && !rc; w++) rc = h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h);
+        for (int w = 0; w < 3 && !rc; w++) rc = launch_nonbonded_p<false>(h);
         if (dual) hipLaunchKernelGGL(k_prune_set, dim3(1, b->R()), dim3(256), 0, h->cur, b->d_core.p, (int*)nullptr, h->n_islots, 2 * mode);   // 2: the kernel leaves the flag up
         if (!rc && hipEventRecord(h->ev0, h->cur) != hipSuccess) rc = 1;
-        for (int r = 0; r < reps && !rc; r++) rc = h->precision == 0 ? launch_nonbonded<float, false>(h) : launch_nonbonded<double, false>(h);
+        for (int r = 0; r < reps && !rc; r++) rc = launch_nonbonded_p<false>(h);
         if (!rc && hipEventRecord(h->ev1, h->cur) != hipSuccess) rc = 1;
         if (rc || hipEventSynchronize(h->ev1) != hipSuccess) { rc = 1; break; }
         hipEventElapsedTime(&ms[mode], h->ev0, h->ev1);

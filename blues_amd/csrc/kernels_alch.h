@@ -56,7 +56,6 @@ struct AlchArgs {
     double* fJ;         // [3 slots][3][n] force on environment atoms by sorted index
     double* self_part;  // [nblocks][3 slots][3][PA]
     double* e_part;     // [nblocks][K2_NP]
-    const DevCtrl* ctrl; // non-null in graph replays: lambda slots come from the device tables
     int* flags_overflow; // -> DevFlags::list_overflow (the dense form: more mobile list entries than it has accumulators for)
     const AtomF* img;    // the fixed-point image (mixed precision; the fp32 dense form stages its records from it), or null
     float fscale[3];     // box edge / 2^32
@@ -83,11 +82,6 @@ __device__ inline bool excluded_sorted(const int* ex_start, const int* ex_idx, i
 template <bool FAST, int MASK = -1, int FORM = 0>
 __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id) {
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
-    if (A.ctrl) {
-        const int L = A.ctrl->L0 + 2 * A.ctrl->kpass;
-#pragma unroll
-        for (int s = 0; s < 3; s++) { const int Ls = min(L + s, A.ctrl->n_lambda); A.ls[s] = A.ctrl->tab_ls[Ls]; A.le[s] = A.ctrl->tab_le[Ls]; }
-    }
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int PA = A.PA;
     const int a = tid & (PA - 1);
@@ -433,11 +427,6 @@ static_assert(sizeof(K2DLds) <= 160 * 1024, "the dense alchemical kernel's recor
 template <int MASK>
 __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
-    if (A.ctrl) {
-        const int L = A.ctrl->L0 + 2 * A.ctrl->kpass;
-#pragma unroll
-        for (int s = 0; s < 3; s++) { const int Ls = min(L + s, A.ctrl->n_lambda); A.ls[s] = A.ctrl->tab_ls[Ls]; A.le[s] = A.ctrl->tab_le[Ls]; }
-    }
     extern __shared__ __align__(16) unsigned char k2d_smem[];
     K2DLds& S = *reinterpret_cast<K2DLds*>(k2d_smem);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -710,11 +699,6 @@ __device__ __forceinline__ void alchemical_dense32_body(AlchArgs& A) {
     constexpr int NS = MASK == 5 ? 2 : (MASK == 2 ? 1 : 3);                    // force slots this instantiation produces
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
     auto slot_ix = [&](int s) -> int { return MASK == 5 ? (s >> 1) : (MASK == 2 ? 0 : s); };   // where slot s lives among the NS accumulators
-    if (A.ctrl) {
-        const int L = A.ctrl->L0 + 2 * A.ctrl->kpass;
-#pragma unroll
-        for (int s = 0; s < 3; s++) { const int Ls = min(L + s, A.ctrl->n_lambda); A.ls[s] = A.ctrl->tab_ls[Ls]; A.le[s] = A.ctrl->tab_le[Ls]; }
-    }
     extern __shared__ __align__(16) unsigned char k2d_smem[];
     K2FLds<NS>& S = *reinterpret_cast<K2FLds<NS>*>(k2d_smem);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;

@@ -47,18 +47,17 @@ struct IntDyn { unsigned draw_base, noise_draw_base; int n_noise, trace_index, t
 __device__ __forceinline__ void apply_dyn(AlchArgs& A, const AlchDyn& d) {
 #pragma unroll
     for (int s = 0; s < 3; s++) { A.ls[s] = d.ls[s]; A.le[s] = d.le[s]; }
-    A.slot_mask = d.slot_mask; A.ctrl = nullptr;
+    A.slot_mask = d.slot_mask;
 }
-__device__ __forceinline__ void apply_dyn(BondedArgs& B, const BondedDyn& d, unsigned delta) { B.draw_base = d.draw_base + delta; B.n_entry_blocks = d.n_entry_blocks; B.ctrl = nullptr; }
+__device__ __forceinline__ void apply_dyn(BondedArgs& B, const BondedDyn& d, unsigned delta) { B.draw_base = d.draw_base + delta; B.n_entry_blocks = d.n_entry_blocks; }
 __device__ __forceinline__ void apply_dyn(FinArgs& F, const FinDyn& d) {
 #pragma unroll
     for (int s = 0; s < 3; s++) F.le[s] = d.le[s];
-    F.slot_mask = d.slot_mask; F.ctrl = nullptr;
+    F.slot_mask = d.slot_mask;
 }
 __device__ __forceinline__ void apply_dyn(IntArgs& A, const IntDyn& d, unsigned delta) {
     A.draw_base = d.draw_base + delta; A.noise_draw_base = d.noise_draw_base + delta; A.n_noise = d.n_noise; A.trace_index = d.trace_index;
     if (!d.tracing) A.work_trace = nullptr;
-    A.ctrl = nullptr;
     A.fin_le[0] = d.fin_le[0]; A.fin_le[1] = d.fin_le[1]; A.fin_le[2] = d.fin_le[2]; A.fin_mask = d.fin_mask;
 }
 
@@ -67,8 +66,8 @@ __device__ __forceinline__ void apply_dyn(IntArgs& A, const IntDyn& d, unsigned 
 // that find nothing to do, each a 1024-thread workgroup that wants ~100 KB of LDS and is alone on its CU while it finds out
 // (R = 512: 5,120 of them, twenty rounds of dispatch for ~200 with work).  Instead one small kernel writes the ordered list of
 // the members that rebuild (work[0] = how many, work[1..] = which) and the rebuild kernels run a SMALL grid whose workgroups
-// deal the (member, tile) items of those members among themselves.  The alchemical kernel uses the same list to run in two
-// parts (k_alchemical_b): the members that do not rebuild need nothing from the rebuild and start beside it.
+// deal the (member, tile) items of those members among themselves.  The fp32 dense alchemical kernel uses the same list to run in
+// two parts (k_alchemical_dense32_b): the members that do not rebuild need nothing from the rebuild and start beside it.
 template <typename R>
 __global__ void __launch_bounds__(LIST_THREADS) k_gather_stale_b(const RepNb<R>* __restrict__ reps, int nrep, int force, int* __restrict__ work) {   // work[1 + nrep + r] = member r rebuilds (0 / 1)
     __shared__ int s_cnt[LIST_WAVES]; __shared__ int s_base;
@@ -230,26 +229,12 @@ __global__ void __launch_bounds__(256) k_gather_pme_e_b(const RepNb<R>* __restri
     if (r < nrep) out[r] = reps[r].active && reps[r].pme.epart ? reps[r].pme.epart[0] : 0.0;
 }
 
-// stale: null = every member; else the work list of the rebuild (k_gather_stale_b): the members that rebuild are left to
-// k_alchemical_stale_b, which follows the rebuild of the group lists (the alchemical tile's records are among them)
 template <bool FAST, int MASK, int FORM = 0>
-__global__ void __launch_bounds__(256, 3) k_alchemical_b(const RepCore* __restrict__ reps, AlchDyn d, int nb, int nrep, const int* __restrict__ stale) {
+__global__ void __launch_bounds__(256, 3) k_alchemical_b(const RepCore* __restrict__ reps, AlchDyn d, int nb, int nrep) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     if (!reps[rep].active) return;
-    if (stale && stale[1 + nrep + rep]) return;
     AlchArgs A = reps[rep].al; apply_dyn(A, d);
     alchemical_blocks<FAST, MASK, FORM>(A, bx, nb - 1);
-}
-
-template <bool FAST, int MASK>
-__global__ void __launch_bounds__(256, 3) k_alchemical_stale_b(const RepCore* __restrict__ reps, AlchDyn d, int nb, const int* __restrict__ work) {
-    const int nact = work[0];
-    for (int i = blockIdx.x; i < nact * nb; i += gridDim.x) {
-        const int m = i / nb;
-        AlchArgs A = reps[work[1 + m]].al; apply_dyn(A, d);
-        alchemical_blocks<FAST, MASK>(A, i - m * nb, nb - 1);
-        __syncthreads();   // (the next item reuses the LDS staging)
-    }
 }
 
 // dense form of the env pairs (kernels_alch.h: alchemical_dense_body): one workgroup per member
@@ -299,21 +284,6 @@ __global__ void __launch_bounds__(256) k_forces_fused_b(const RepNb<R>* __restri
         return;
     }
     if (b < nb1 + nb2) { AlchArgs A = reps[blockIdx.y].al; apply_dyn(A, da); alchemical_body<sizeof(R) == 4>(A, b - nb1); return; }
-    BondedArgs B = reps[blockIdx.y].bo; apply_dyn(B, db, reps[blockIdx.y].draw_delta);
-    bonded_entries_body(B, b - nb1 - nb2, 256);
-}
-
-template <int IW>
-__global__ void __launch_bounds__(256) k_forces_fused_sub_b(const RepNb<float>* __restrict__ rnb, const RepCore* __restrict__ reps, AlchDyn da, BondedDyn db, int nb1, int nb2) {
-    if (!reps[blockIdx.y].active) return;
-    const int b = blockIdx.x;
-    if (b < nb2) { AlchArgs A = reps[blockIdx.y].al; apply_dyn(A, da); alchemical_body<true>(A, b); return; }
-    if (b < nb2 + nb1) {
-        const RepNb<float>& rp = rnb[blockIdx.y];
-        const NbArgs<float> a = rp.nb; const NbConst<float> c = rp.c;
-        nonbonded_sub_body<false, IW>(a, c, rp.img, b - nb2);
-        return;
-    }
     BondedArgs B = reps[blockIdx.y].bo; apply_dyn(B, db, reps[blockIdx.y].draw_delta);
     bonded_entries_body(B, b - nb1 - nb2, 256);
 }

@@ -42,7 +42,6 @@ struct BondedArgs {
     int n_mobile, n_noise; const int* mobile_atoms; double* noise;  // noise[(d*3+k)*n_mobile + m]
     unsigned long long seed; unsigned stream, draw_base;
     int n_entry_blocks;
-    const DevCtrl* ctrl;
     // centroid bonds: 2 * CENT_GROUP atoms and 2 * CENT_GROUP weights + k per term
     int n_cent; const int* cent_atoms; const double* cent_params;
 };
@@ -178,8 +177,7 @@ __device__ __forceinline__ void bonded_entries_body(const BondedArgs& B, const i
         if (g >= B.n_mobile * B.n_noise) return;
         const int d = g / B.n_mobile, m = g - d * B.n_mobile;
         double z[3];
-        const unsigned base = B.ctrl ? B.ctrl->draw0 + (unsigned)B.ctrl->kpass : B.draw_base;
-        gaussians3(B.seed, B.stream, base + (unsigned)d, (unsigned)B.mobile_atoms[m], z);
+        gaussians3(B.seed, B.stream, B.draw_base + (unsigned)d, (unsigned)B.mobile_atoms[m], z);
         for (int k = 0; k < 3; k++) B.noise[(size_t)(d * 3 + k) * B.n_mobile + m] = z[k];
         return;
     }

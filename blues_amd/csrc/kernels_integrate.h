@@ -87,7 +87,6 @@ struct IntArgs {
     double total_mass; double* cm_part; int cm_nblocks;
     const double* mom_part; int n_mom;  // momentum partials written by k_finalize (see FinArgs)
     DevAccum* acc; double* work_trace; int trace_index;
-    DevCtrl* ctrl;
     long long* stamps;  // debug builds (-DBLUES_STAMP): cycle stamp of thread 0 at every op boundary
     Program prog;
 };
@@ -399,7 +398,6 @@ struct FinArgs {
     double le[3];
     int slot_mask;              // lambda slots whose force will be applied (bit s); the others are neither read nor written
     double* ftot; double* alch_self; DevAccum* acc;
-    DevCtrl* ctrl;
     // momentum bookkeeping for CMMotionRemover without a grid-wide reduction inside the step kernel:
     // mom_part[block][0..2] = sum m v, [3..5] = sum of the slot-0 force, over the block's atoms
     const double* v[3]; const double* mass; double* mom_part;
@@ -415,12 +413,6 @@ struct FinArgs {
 template <bool LEAN>   // (LEAN: kept as a name of the batched instantiation; the sums are the same shared functions either way)
 __device__ __forceinline__ void finalize_body(FinArgs& A) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (A.ctrl) {
-        const int L = A.ctrl->L0 + 2 * A.ctrl->kpass;
-#pragma unroll
-        for (int s = 0; s < 3; s++) A.le[s] = A.ctrl->tab_le[min(L + s, A.ctrl->n_lambda)];
-        if (blockIdx.x == 0 && tid == 0) A.ctrl->kint = A.ctrl->kpass;  // nothing in this kernel reads kint
-    }
     const int n_itiles = A.n_islots / 64;
     const int nb_alch_atoms = A.n_alch > 0 ? 1 : 0;
     int blk = blockIdx.x;
@@ -507,11 +499,6 @@ __global__ void __launch_bounds__(256) k_finalize(FinArgs A) { finalize_body<fal
 // kernel arguments while A is a per-replica copy
 __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) {
     const int tid = threadIdx.x;
-    if (A.ctrl) {
-        const int u = A.ctrl->kint;
-        A.draw_base = A.ctrl->draw0 + (unsigned)u; A.noise_draw_base = A.draw_base; A.trace_index = A.ctrl->trace0 + u;
-        if (blockIdx.x == 0 && tid == 0) A.ctrl->kpass = u + 1;  // nothing in this kernel reads kpass
-    }
     const int cl = blockIdx.x * blockDim.x + tid;
     __shared__ double s_red[4][4];
     __shared__ double s_cm[3];
@@ -910,11 +897,6 @@ __device__ __forceinline__ void step_default_body(IntArgs& A) {
     const int tid = threadIdx.x;
     STEP_STAMP(0);
     const int cl = blockIdx.x * blockDim.x + tid;
-    if (A.ctrl) {
-        const int u = A.ctrl->kint;
-        A.draw_base = A.ctrl->draw0 + (unsigned)u; A.noise_draw_base = A.draw_base; A.trace_index = A.ctrl->trace0 + u;
-        if (blockIdx.x == 0 && tid == 0) A.ctrl->kpass = u + 1;
-    }
     __shared__ double s_red[4][4];
     __shared__ double s_cm[3];
     const bool active = cl < A.n_clusters;
@@ -1264,14 +1246,3 @@ __device__ __forceinline__ void step_md_body(IntArgs& A) {
 
 template <bool CM>
 __global__ void __launch_bounds__(256) k_step_md(IntArgs A) { step_md_body<CM>(A); }
-
-// the same role dispatch around the sub-tile throughput kernel (large i-sets): the alchemical and bonded blocks are
-// queued behind the nonbonded ones and fill CUs as those drain, instead of costing two more launches
-template <int IW>
-__global__ void __launch_bounds__(256) k_forces_fused_sub(NbArgs<float> a, NbConst<float> c, const AtomF* __restrict__ img,
-                                                          AlchArgs A, BondedArgs B, int nb1, int nb2) {
-    const int b = blockIdx.x;
-    if (b < nb2) { alchemical_body<true>(A, b); return; }             // the longest-latency blocks first
-    if (b < nb2 + nb1) { nonbonded_sub_body<false, IW>(a, c, img, b - nb2); return; }
-    bonded_entries_body(B, b - nb1 - nb2, 256);
-}

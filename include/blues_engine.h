@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BLUES_ABI_VERSION 7
+#define BLUES_ABI_VERSION 8
 
 /* nonbonded_method */
 #define BLUES_NB_NOCUTOFF 0   /* vacuum: every pair, bare Coulomb, no periodicity; the box is stored and has no effect */
@@ -177,7 +177,7 @@ int blues_abi_version(void);
  * the library reads NO environment variables.  The process-wide tuning is copied
  * into every engine and batch when it is created; none of it changes results
  * beyond floating-point summation order (pruned lists, list margins) or nothing
- * at all (stream forks, graph replay, capacities).
+ * at all (stream forks, capacities).
  * -1 / 0 = "engine default" unless stated otherwise. */
 typedef struct BluesTuning {
     int32_t struct_size;       /* sizeof(BluesTuning) of the caller: set by blues_tuning_default */
@@ -198,9 +198,7 @@ typedef struct BluesTuning {
     int32_t waves_per_block;   /* tile kernel; 0 auto */
     int32_t k2_jiter;          /* j groups per environment block of the alchemical kernel; 0 auto */
     int32_t fuse_forces;       /* -1 auto; 0 / 1: separate force kernels / one launch with block roles */
-    int32_t fuse_big;          /* -1 auto (off) */
     int32_t fast_step;         /* -1 auto (on): straight-line step kernels */
-    int32_t slot_mask;         /* -1 auto; else the lambda slots whose force a pass produces */
     int32_t fork;              /* 1 (default): a batch runs the alchemical / bonded kernels on a side stream beside the builder of the atoms'
                                 * lists -- of a pass with the dense alchemical kernel only the two small ones (alchemical x alchemical block,
                                 * bonded entries); 0: every kernel alone; 2: the dense kernel too, joined before the nonbonded kernel (no gain);
@@ -208,9 +206,6 @@ typedef struct BluesTuning {
                                 * 4: the small kernels and the dense kernel of the members that do not rebuild their lists beside the work list
                                 * and the group-list builder (which leave the chip idle), the dense kernel of the others behind the group lists;
                                 * all joined before the nonbonded kernel */
-    int32_t use_graph;         /* -1 auto (off): hipGraph replay of the steady-state step of a lone engine */
-    int32_t graph_units;       /* 0 auto */
-    int32_t graph_fork;        /* -1 auto (off) */
     int32_t batch_sync_lists;  /* 1: every member of a batch rebuilds when one asks (drops batch = solo bitwise identity) */
     int32_t force_lists;       /* 1: rebuild the lists at every launch (development) */
     int32_t no_sphere;         /* 1: bounding-box list test only (development) */
@@ -223,8 +218,6 @@ typedef struct BluesTuning {
     int32_t k2_dense;          /* -1 auto (on where it applies: large batch, mixed precision, free alchemical group of <= 16 atoms);
                                 * 0: the alchemical kernel keeps its (atom, list entry) lane layout; 2: the dense form with the fp64 pair
                                 * arithmetic of round 5 (the reference the fp32 form of round 6 is tested against) */
-    int32_t k2_early;          /* 1: with `fork`, the alchemical kernel of the members of a batch that do not rebuild their lists
-                                * in a force pass starts beside the rebuild of the others; 0 (default): after the group lists */
     int32_t fuse_finalize;     /* 1 (default): where one workgroup holds every constraint cluster of a chain, the steady-state step kernel
                                 * forms the summed forces of the pass itself (no k_finalize launch); 0: always the separate kernel */
     int32_t host_threads;      /* host threads for work the members of a batch share (re-sorts and re-layouts of several members at a poll);

@@ -1,5 +1,5 @@
 """One chain to the letter (configs[1]): step time of a lone S23k engine under a few tuning specs.
-   python scripts/dev_single.py "" "use_graph=1" "use_graph=1,graph_units=32" ..."""
+   python scripts/dev_single.py "" "fuse_finalize=0" "fast_step=0,fuse_finalize=0" ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from blues_amd import build, integrators, systems, tuning
