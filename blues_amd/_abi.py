@@ -9,7 +9,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 SWITCH_NONE, SWITCH_VV, SWITCH_GHMC = 0, 1, 2
 NB_NOCUTOFF = 0
 NB_PME_DIRECT = 1
@@ -60,6 +60,7 @@ class BluesIntegratorDesc(C.Structure):
         ("constraint_tolerance", C.c_double),
         ("seed", C.c_uint64), ("replica", C.c_int32), ("precision", C.c_int32),
         ("switching_mode", C.c_int32), ("steps_per_propagation", C.c_int32),
+        ("measure_shadow_work", C.c_int32), ("measure_heat", C.c_int32),
     ]
 
 
@@ -242,6 +243,8 @@ class IntegratorData:
     precision: int = 0                   # 0 mixed, 1 double
     switching_mode: int = 0              # SWITCH_NONE / SWITCH_VV / SWITCH_GHMC (reference blues/switching.py)
     steps_per_propagation: int = 1
+    measure_shadow_work: int = 0         # SWITCH_NONE only: book the shadow work of the R and V substeps on the device
+    measure_heat: int = 0                # SWITCH_NONE only: book the heat of the O substeps
 
     @property
     def n_lambda_steps(self):
@@ -250,6 +253,8 @@ class IntegratorData:
         return int(self.nsteps_neq) * self.splitting.count("H")
 
     def to_desc(self):
+        if self.switching_mode and (self.measure_shadow_work or self.measure_heat):
+            raise ValueError("measure_shadow_work / measure_heat belong to the Langevin switch: a switching_mode integrator keeps its own shadow work")
         keep = {}
         d = BluesIntegratorDesc()
         d.timestep = float(self.timestep); d.temperature = float(self.temperature)
@@ -268,6 +273,7 @@ class IntegratorData:
         d.constraint_tolerance = float(self.constraint_tolerance)
         d.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF; d.replica = int(self.replica); d.precision = int(self.precision)
         d.switching_mode = int(self.switching_mode); d.steps_per_propagation = int(self.steps_per_propagation)
+        d.measure_shadow_work = int(bool(self.measure_shadow_work)); d.measure_heat = int(bool(self.measure_heat))
         return d, keep
 
 

@@ -242,6 +242,10 @@ struct BluesEngine {
     double sw_Epert = 0.0, sw_shadow = 0.0, sw_Einit = 0.0, sw_Efinal = 0.0, sw_bracket_E0 = 0.0; int sw_accept = 0, sw_naccept = 0, sw_ntrials = 0;
     unsigned sw_draw = 0;   // Metropolis uniforms drawn so far by the GHMC integrator: the Philox counter; reset() does NOT touch it (ntrials is a statistic)
     bool sw_bracket_open = false; struct BluesSnapshot* sw_saved = nullptr;
+    // the energy ledger of the Langevin switch (BluesIntegratorDesc::measure_shadow_work / measure_heat).  led_flags: LED_* bits.
+    // led_open: DevAccum::u_open holds U(x, lambda_current) of the positions the pending stretch of R substeps started from;
+    // led_dirty: an R substep has moved the atoms since (its potential-energy change is still to be booked: ledger_close)
+    int led_flags = 0; bool led_open = false, led_dirty = false; DBuf<double> d_led_part;
     std::vector<double> tab_ls, tab_le;
     uint64_t seed = 0; int replica = 0;
     // ---- mirrored control state
@@ -716,6 +720,7 @@ static int build_clusters(BluesEngine* h, const BluesSystemDesc* s) {
     h->int_threads = ncl <= 256 ? std::max(128, ((ncl + 63) / 64) * 64) : 256;
     h->int_blocks = std::max(1, (ncl + h->int_threads - 1) / h->int_threads);
     h->d_cm_part.alloc((size_t)h->int_blocks * 3);
+    if (h->led_flags) h->d_led_part.alloc((size_t)h->int_blocks * 2);
     return 0;
 }
 
@@ -1342,6 +1347,7 @@ static IntArgs make_int_args(BluesEngine* h) {
     A.total_mass = h->total_mass; A.cm_part = h->d_cm_part.p; A.cm_nblocks = h->int_blocks;
     A.mom_part = h->d_mom_part.p; A.n_mom = h->n_islots / 64 + 2;
     A.acc = h->d_acc.p; A.work_trace = h->tracing ? h->d_trace.p : nullptr; A.trace_index = h->prog_trace;
+    A.led_part = h->d_led_part.p; A.led_flags = h->led_flags;
     A.stamps = h->d_stamps.p;
     A.prog = h->prog;
     return A;
@@ -1385,7 +1391,12 @@ static int flush_program(BluesEngine* h) {
         else if (!dry) hipLaunchKernelGGL(k_step_md<false>, grid, block, 0, h->cur, A);
     } else {
         if (has_part) E_FAIL(h, "internal: OP_CM_PART outside a specialised program");
-        if (lead) hipLaunchKernelGGL(k_integrate_b, grid, block, 0, h->cur, reps, D);
+        if (h->led_flags) {   // the measuring interpreter, then the blocks' KE partials in block order (energy ledger)
+            if (lead) { hipLaunchKernelGGL(k_integrate_led_b, grid, block, 0, h->cur, reps, D); hipLaunchKernelGGL(k_ledger_ke_b, dim3(h->batch->R()), dim3(64), 0, h->cur, reps); }
+            else if (!dry) { hipLaunchKernelGGL(k_integrate_led, grid, block, 0, h->cur, A); hipLaunchKernelGGL(k_ledger_ke, dim3(1), dim3(64), 0, h->cur, h->d_acc.p, h->d_led_part.p, h->int_blocks, h->led_flags); }
+            h->st_launches++;
+        }
+        else if (lead) hipLaunchKernelGGL(k_integrate_b, grid, block, 0, h->cur, reps, D);
         else if (!dry) hipLaunchKernelGGL(k_integrate, grid, block, 0, h->cur, A);
     }
     h->vel_clean = false;
@@ -2443,6 +2454,42 @@ static int add_work(BluesEngine* h, double delta) {
     return 0;
 }
 
+// ---- energy ledger: the potential-energy part of the shadow work.  V and O do not move atoms, so the R increments of a
+// stretch at constant lambda telescope to U(x_after) - U(x_before); OP_H carries u_open from one lambda to the next with the slot
+// difference it books as protocol work.  What is left is ONE energy-form pass (energy_launch: the energy forms of the pass's own kernels)
+// at the end of every stretch -- where the next force pass is due anyway -- and one where a stretch starts from positions set from
+// outside.  Its partials are summed on the device (k_ledger_pe): no read-back, no host synchronisation.
+static int ledger_pe(BluesEngine* h, int close) {
+    if (energy_launch(h)) return 1;   // (flushes the pending program first; leaves pass_valid = false)
+    const EnergyShape g = energy_shape(h);
+    LedgerPe L; memset(&L, 0, sizeof L);
+    L.enb = h->d_epart_nb.p; L.eb = h->d_epart_b.p; L.ep = h->alch.empty() ? nullptr : h->d_e_part.p; L.jcount = h->d_jcount.p + h->n_lists;
+    L.e_mesh = h->pme ? h->d_pme_e.p : nullptr;
+    L.nw = g.nw; L.nbb = g.nbb; L.PA = h->PA; L.k2_jiter = h->k2_jiter; L.k2_nblocks_env = h->k2_nblocks_env; L.le = h->cur_le;
+    L.acc = h->d_acc.p; L.close = close;
+    if (batch_lead(h)) {
+        if (h->precision == 0) hipLaunchKernelGGL(k_ledger_pe_b<float>, dim3(h->batch->R()), dim3(64), 0, h->cur, h->batch->d_nb_f.p, h->batch->d_core.p, L);
+        else hipLaunchKernelGGL(k_ledger_pe_b<double>, dim3(h->batch->R()), dim3(64), 0, h->cur, h->batch->d_nb_d.p, h->batch->d_core.p, L);
+    } else if (!batch_dry(h)) hipLaunchKernelGGL(k_ledger_pe, dim3(1), dim3(64), 0, h->cur, L);
+    h->st_launches++; h->acc_cache_valid = false;
+    HIP_OK(h, hipGetLastError());
+    h->led_open = true; h->led_dirty = false;
+    return 0;
+}
+static inline bool ledger_on(const BluesEngine* h) { return (h->led_flags & LED_SHADOW) != 0; }
+// before an R substep is emitted
+static int ledger_before_R(BluesEngine* h) {
+    if (!ledger_on(h)) return 0;
+    if (!h->led_open && ledger_pe(h, 0)) return 1;
+    h->led_dirty = true;
+    return 0;
+}
+// the pending stretch ends at the current positions (a force pass is due here, or the stepping call returns)
+static int ledger_close(BluesEngine* h) {
+    if (!ledger_on(h) || !h->led_dirty) return 0;
+    return ledger_pe(h, 1);
+}
+
 static int emit_cm(BluesEngine* h) {
     if (!h->remove_cm) return 0;
     if (h->fast_step && h->vel_clean && h->pass_valid && (h->pass_fmask & 1)) {  // the momentum partials are built from slot-0 forces
@@ -2459,6 +2506,7 @@ static int emit_cm(BluesEngine* h) {
 static int need_pass(BluesEngine* h, int lo, int hi) {  // need slots covering L in [lo, hi] of the current x
     if (h->pass_valid && lo - h->pass_L >= 0 && hi - h->pass_L <= 2) return 0;
     if (flush_program(h)) return 1;
+    if (ledger_close(h)) return 1;   // (energy ledger: the R stretch that led here ends where this pass is evaluated)
     return force_pass(h, lo);
 }
 
@@ -2488,7 +2536,7 @@ static int run_fragment(BluesEngine* h, const std::string& frag) {
             if (emit(h, OP_A0 + (h->h_lambda_step - h->pass_L))) return 1;
             h->pass_valid = false;
         } break;
-        case 'R': if (emit(h, OP_R)) return 1; h->pass_valid = false; break;
+        case 'R': if (ledger_before_R(h) || emit(h, OP_R)) return 1; h->pass_valid = false; break;
         case 'O':
             if (h->switch_mode == BLUES_SWITCH_GHMC && ci + 1 < frag.size() && frag[ci + 1] == 'A' && emit_cm(h)) return 1;   // addUpdateContextState ahead of the first randomisation, switching.py:976
             if (emit(h, OP_O)) return 1;
@@ -2591,7 +2639,8 @@ static int step_head(BluesEngine* h) {
         if (emit(h, OP_PREP)) return 1;
         if (flush_program(h)) return 1;
         h->pass_valid = false;
-        HIP_OK(h, hipMemsetAsync(h->d_acc.p, 0, sizeof(DevAccum), h->stream));
+        if (h->led_flags) { hipLaunchKernelGGL(k_ledger_reset, dim3(1), dim3(1), 0, h->stream, h->d_acc.p, 0); h->st_launches++; h->led_open = false; h->led_dirty = false; }   // (heat and shadow_work are not the first-step block's to zero)
+        else HIP_OK(h, hipMemsetAsync(h->d_acc.p, 0, sizeof(DevAccum), h->stream));
         h->acc_cache_valid = false;
         h->h_lambda = 0.0; h->h_lambda_step = 0; h->cur_ls = h->tab_ls[0]; h->cur_le = h->tab_le[0];
         h->h_perturbed = h->h_unperturbed = 0.0; h->unpert_valid = false;
@@ -2641,6 +2690,7 @@ static int do_steps(BluesEngine* h, int nsteps) {
         if (step_head(h)) return 1;
         if (step_body(h)) return 1;
     }
+    if (ledger_close(h)) return 1;   // (energy ledger: what the caller reads next is complete)
     return flush_program(h);
 }
 
@@ -2651,6 +2701,7 @@ struct BatchSig {
     int h_step, h_lambda_step, h_prop, h_first_step, pass_L, prog_n, prog_trace, nprop;
     unsigned h_draw, prog_draw_base, noise_draw_base;
     unsigned char pass_valid, lists_forced, vel_clean, noise_valid, tracing, sorted_ok, pass_valid_for_l, have_positions, fin_pending, fin_mask;
+    unsigned char led_open, led_dirty;   // (energy ledger: where the member stands in its R stretch decides on launches)
     unsigned char ops[MAX_OPS];
 };
 static int batch_enter(BluesBatch* B) {
@@ -2685,6 +2736,7 @@ static BatchSig batch_sig(const BluesEngine* h) {
     g.pass_valid = h->pass_valid; g.lists_forced = h->lists_forced; g.vel_clean = h->vel_clean; g.noise_valid = h->noise_valid; g.tracing = h->tracing;
     g.sorted_ok = h->sorted_ok; g.pass_valid_for_l = h->pass_valid_for_l; g.have_positions = h->have_positions;
     g.fin_pending = h->fin_pending; g.fin_mask = g.fin_pending ? (unsigned char)h->fin_mask : 0;   // (what flush_program decides on: members in lock step must agree)
+    g.led_open = h->led_open; g.led_dirty = h->led_dirty;
     for (int q = 0; q < h->prog.n; q++) g.ops[q] = h->prog.ops[q];
     return g;
 }
@@ -2692,6 +2744,7 @@ static BatchSig batch_sig(const BluesEngine* h) {
 // static shape of a member: launch geometry and protocol.  All members must agree.
 static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const char** why) {
     if (nocut(a) != nocut(b)) { *why = "nonbonded method (a NoCutoff engine and a periodic one cannot share a batch)"; return false; }
+    if (a->led_flags != b->led_flags) { *why = "measure_shadow_work / measure_heat (measuring and non-measuring members cannot share a batch)"; return false; }
     if (a->pair_mode != b->pair_mode || a->n_cent != b->n_cent) { *why = "custom forces (members with and without the custom pair form or centroid bonds cannot share a batch)"; return false; }
 #define BC(f) if (a->f != b->f) { *why = #f; return false; }
     BC(device) BC(n) BC(precision) BC(nsteps) BC(nprop) BC(n_lambda) BC(split) BC(remove_cm) BC(dt) BC(gamma) BC(kT) BC(tol) BC(prop_min) BC(prop_max)
@@ -2892,17 +2945,17 @@ static int batch_prefetch(BluesBatch* B, int what) {
             std::vector<double> ke;
             try {
                 if (ok) {
-                    if (B->d_gather.n < (size_t)7 * R) B->d_gather.alloc((size_t)7 * R);
+                    if (B->d_gather.n < (size_t)9 * R) B->d_gather.alloc((size_t)9 * R);
                     hipLaunchKernelGGL(k_kinetic_b, dim3(R), dim3(256), 0, B->stream, B->d_core.p, B->d_gather.p);
                     ok = hipStreamSynchronize(B->stream) == hipSuccess;
-                    if (ok) { ke.resize((size_t)7 * R); ok = hipMemcpy(ke.data(), B->d_gather.p, sizeof(double) * 7 * R, hipMemcpyDeviceToHost) == hipSuccess; }
+                    if (ok) { ke.resize((size_t)9 * R); ok = hipMemcpy(ke.data(), B->d_gather.p, sizeof(double) * 9 * R, hipMemcpyDeviceToHost) == hipSuccess; }
                 }
             } catch (std::string& e) { B->err = e; ok = false; }
             if (ok) for (int r = 0; r < R; r++) if (live[r]) {
                 BluesEngine* m = B->eng[r];
                 m->ke_cache = ke[r]; m->ke_cache_valid = true;
-                static_assert(sizeof(DevAccum) == 6 * sizeof(double), "k_kinetic_b copies six doubles");
-                memcpy(&m->acc_cache, &ke[(size_t)R + 6 * r], sizeof(DevAccum)); m->acc_cache_valid = true; m->acc_cache_stamp = m->st_launches;
+                static_assert(sizeof(DevAccum) == 8 * sizeof(double), "k_kinetic_b copies eight doubles");
+                memcpy(&m->acc_cache, &ke[(size_t)R + 8 * r], sizeof(DevAccum)); m->acc_cache_valid = true; m->acc_cache_stamp = m->st_launches;
             }
             B->st_prefetch_ke++;
         }
@@ -3073,6 +3126,11 @@ static int batch_do_steps(BluesBatch* B, int n_steps, bool tracing, int* status)
         }
         if (phase(step_body)) return 1;
     }
+    {   // energy ledger: a measuring batch books the R stretch that is still pending, so that what the caller reads next is complete
+        bool pending = false;
+        for (int r = 0; r < R; r++) pending |= !B->failed[r] && ledger_on(B->eng[r]) && B->eng[r]->led_dirty;
+        if (pending && phase(ledger_close)) return 1;
+    }
     if (phase(flush_program)) return 1;
     for (int r = 0; r < R; r++) B->eng[r]->tracing = false;
     // error flags: one gathered read-back tells which members (normally none) need their own check_flags
@@ -3198,6 +3256,8 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
     h->tol = it->constraint_tolerance; h->nsteps = it->nsteps_neq; h->nprop = it->nprop; h->n_lambda = it->n_lambda_steps;
     h->prop_min = it->prop_lambda_min; h->prop_max = it->prop_lambda_max; h->seed = it->seed; h->replica = it->replica; h->precision = it->precision;
     h->switch_mode = it->switching_mode; h->psteps = it->steps_per_propagation;
+    h->led_flags = (it->measure_heat ? LED_HEAT : 0) | (it->measure_shadow_work ? LED_SHADOW : 0);
+    if (h->led_flags && h->switch_mode != BLUES_SWITCH_NONE) E_FAIL(h, "measure_shadow_work / measure_heat belong to the Langevin switch (BLUES_SWITCH_NONE): the velocity-Verlet switching integrator keeps its own shadow work, the GHMC one has none");
     if (h->switch_mode != BLUES_SWITCH_NONE) {
         if (h->switch_mode != BLUES_SWITCH_VV && h->switch_mode != BLUES_SWITCH_GHMC) E_FAIL(h, "unknown switching_mode %d", h->switch_mode);
         if (h->psteps < 0 || h->nsteps < 1) E_FAIL(h, "switching integrators need nsteps_neq >= 1 and steps_per_propagation >= 0");
@@ -3231,6 +3291,7 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
     }
     h->cur = h->stream;
     if (h->tune.fast_step >= 0) h->fast_step = h->tune.fast_step != 0;
+    if (h->led_flags) h->fast_step = false;   // a measuring engine steps through the general interpreter and k_finalize: the fused step kernels stay as they are
     try {
         for (int k = 0; k < 3; k++) { h->d_x[k].alloc(n); h->d_v[k].alloc(n); h->d_xbuild[k].alloc(n); h->d_x_sort[k].alloc(n); }
         h->d_stage.alloc((size_t)3 * n); h->d_xfer_out.alloc(4);
@@ -3550,7 +3611,7 @@ static int load_positions(BluesEngine* h, const double* const src[3], int stride
     if (!h->h_xfer && hipHostMalloc((void**)&h->h_xfer, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) E_FAIL(h, "hipHostMalloc failed");
     HIP_OK(h, hipMemcpyAsync(h->h_xfer, h->d_xfer_out.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     h->xfer_pending = true; h->xfer_stream = h->stream; h->xfer_src = h->h_xfer;
-    h->have_positions = true; h->x_edited = true; h->pass_valid = false; h->fin_pending = false; h->ecache.clear();
+    h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false; h->ecache.clear();
     h->lists_forced = true;
     return 0;
 }
@@ -3583,7 +3644,7 @@ int blues_set_positions(BluesEngine* h, const double* xyz, int32_t n_atoms) {
         HIP_OK(h, hipStreamSynchronize(h->stream));
         h->hx = st;
         if (upload_xyz(h, h->hx.data(), h->d_x)) return 1;
-        h->have_positions = true; h->x_edited = true; h->pass_valid = false; h->fin_pending = false; h->ecache.clear(); h->e_frozen_valid = false; h->pme_static_valid = false;
+        h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false; h->ecache.clear(); h->e_frozen_valid = false; h->pme_static_valid = false;
         return sort_and_tile(h);
     }
     // one interleaved transfer; de-interleaving, image refresh and the re-sort statistics happen on the device
@@ -3602,6 +3663,7 @@ int blues_set_velocities(BluesEngine* h, const double* xyz, int32_t n_atoms) {
 }
 
 int blues_set_box(BluesEngine* h, const double box[9]) {
+    h->led_open = false; h->led_dirty = false;   // (energy ledger: U(x) is a function of the box; the bracket restarts)
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) if (r != c && box[3 * r + c] != 0.0) E_FAIL(h, "only orthorhombic boxes are supported");
     if (box[0] == h->box[0] && box[4] == h->box[1] && box[8] == h->box[2]) return 0;
     HIP_OK(h, hipSetDevice(h->device));
@@ -3766,7 +3828,11 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
     else if (k == "n_lambda_steps") *value = h->n_lambda;
     else if (k == "nsteps") *value = h->nsteps;
     else if (k == "protocol_work") { if (read_acc(h, &a)) return 1; *value = a.protocol_work; }
-    else if (k == "shadow_work") *value = h->switch_mode != BLUES_SWITCH_NONE ? h->sw_shadow : 0.0;
+    else if (k == "shadow_work") {
+        if (h->switch_mode != BLUES_SWITCH_NONE) *value = h->sw_shadow;
+        else if (h->led_flags & LED_SHADOW) { if (read_acc(h, &a)) return 1; *value = a.shadow_work; }
+        else *value = 0.0;
+    }
     else if (k == "perturbed_pe") *value = h->h_perturbed;
     else if (k == "unperturbed_pe") *value = h->h_unperturbed;
     else if (k == "first_step") *value = h->h_first_step;
@@ -3779,7 +3845,7 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
         if (read_acc(h, &a)) return 1;
         *value = (k == "Enew") ? E : E - a.dE_last;
     }
-    else if (k == "heat") *value = 0.0;
+    else if (k == "heat") { if (h->led_flags & LED_HEAT) { if (read_acc(h, &a)) return 1; *value = a.heat; } else *value = 0.0; }
     else if (k == "kT") *value = h->kT;
     else if (h->switch_mode != BLUES_SWITCH_NONE && (k == "total_work" || k == "Epert" || k == "initial_energy" || k == "final_energy" || k == "accept" || k == "naccept" || k == "ntrials" || k == "psteps")) {
         // globals of reference blues/switching.py:1062-1080, energies in kJ/mol
@@ -3801,15 +3867,15 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
 int blues_set_global(BluesEngine* h, const char* name, double value) {
     HIP_OK(h, hipSetDevice(h->device));
     std::string k(name);
-    if (k == "protocol_work") {
+    if (k == "protocol_work" || (k == "shadow_work" && (h->led_flags & LED_SHADOW)) || (k == "heat" && (h->led_flags & LED_HEAT))) {
         DevAccum a; if (read_acc(h, &a)) return 1;
-        a.protocol_work = value;
+        if (k == "protocol_work") a.protocol_work = value; else if (k == "heat") a.heat = value; else a.shadow_work = value;
         HIP_OK(h, hipMemcpy(h->d_acc.p, &a, sizeof a, hipMemcpyHostToDevice));
         h->acc_cache_valid = false;
     }
     else if (k == "step") h->h_step = (int)value;
     else if (k == "lambda") h->h_lambda = value;
-    else if (k == "lambda_step") { h->h_lambda_step = (int)value; h->pass_valid = false; h->fin_pending = false; }
+    else if (k == "lambda_step") { h->h_lambda_step = (int)value; h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }   // (energy ledger: U changes from outside, the bracket restarts)
     else if (k == "first_step") h->h_first_step = (int)value;
     else if (k == "prop") h->h_prop = (int)value;
     else if (k == "nprop") h->nprop = (int)value;
@@ -3819,8 +3885,8 @@ int blues_set_global(BluesEngine* h, const char* name, double value) {
     else if (h->switch_mode != BLUES_SWITCH_NONE && (k == "total_work" || k == "naccept" || k == "ntrials")) {
         if (k == "naccept") h->sw_naccept = (int)value; else if (k == "ntrials") h->sw_ntrials = (int)value;   // (total_work is derived)
     }
-    else if (k == "lambda_sterics") { h->cur_ls = value; h->pass_valid = false; h->fin_pending = false; }
-    else if (k == "lambda_electrostatics") { h->cur_le = value; h->pass_valid = false; h->fin_pending = false; }
+    else if (k == "lambda_sterics") { h->cur_ls = value; h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }
+    else if (k == "lambda_electrostatics") { h->cur_le = value; h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }
     else E_FAIL(h, "global variable '%s' cannot be set", name);
     return 0;
 }
@@ -3830,7 +3896,8 @@ int blues_reset(BluesEngine* h) {
     if (flush_program(h)) return 1;
     h->h_step = 0; h->h_lambda = 0.0; h->h_first_step = 0; h->h_perturbed = 0.0; h->h_unperturbed = 0.0; h->h_prop = 1; h->h_lambda_step = 0;
     h->unpert_valid = false; h->x_edited = false; h->pass_valid = false; h->fin_pending = false;
-    HIP_OK(h, hipMemsetAsync(h->d_acc.p, 0, sizeof(DevAccum), h->stream));
+    if (h->led_flags) { hipLaunchKernelGGL(k_ledger_reset, dim3(1), dim3(1), 0, h->stream, h->d_acc.p, 1); h->st_launches++; h->led_open = false; h->led_dirty = false; }   // (shadow_work goes, heat stays: orc_reset)
+    else HIP_OK(h, hipMemsetAsync(h->d_acc.p, 0, sizeof(DevAccum), h->stream));
     h->acc_cache_valid = false;
     h->sw_shadow = 0.0; h->sw_Einit = 0.0; h->sw_Efinal = 0.0; h->sw_naccept = 0; h->sw_ntrials = 0; h->sw_accept = 0;   // switching.py:1023-1036
     return 0;
@@ -4453,7 +4520,7 @@ static int batch_restore_impl(BluesBatch* B, BluesSnapshot* const* snaps, int wh
         BluesEngine* h = B->eng[r];
         if (what & 1) {
             h->xfer_pending = true; h->xfer_stream = h->stream; h->xfer_src = B->h_xfer_all + 4 * r; h->xfer_foreign = snaps[r]->owner != h;
-            h->have_positions = true; h->x_edited = true; h->pass_valid = false; h->fin_pending = false; h->ecache.clear(); h->lists_forced = true;
+            h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false; h->ecache.clear(); h->lists_forced = true;
             h->st_launches += n_idx > 0 ? 2 : 1;
             if (snaps[r]->owner == h && n_idx == 0 && snaps[r]->box_epoch == h->box_epoch) h->ecache = snaps[r]->ecache;   // the energy that was known for these positions (in this box) is known again
             if (resolve_xfer(h)) { B->err = h->err; return 1; }   // (already on the host: no wait)
@@ -4518,7 +4585,7 @@ int blues_batch_reset(BluesBatch* B, const int32_t* mask) {
         if (mask && !mask[r]) continue;
         acc[r] = h->d_acc.p;
         h->h_step = 0; h->h_lambda = 0.0; h->h_first_step = 0; h->h_perturbed = 0.0; h->h_unperturbed = 0.0; h->h_prop = 1; h->h_lambda_step = 0;
-        h->unpert_valid = false; h->x_edited = false; h->pass_valid = false; h->fin_pending = false; h->acc_cache_valid = false;
+        h->unpert_valid = false; h->x_edited = false; h->pass_valid = false; h->fin_pending = false; h->acc_cache_valid = false; h->led_open = false; h->led_dirty = false;
     }
     int rc = batch_arena_upload(B, sizeof(DevAccum*) * R);
     if (!rc) hipLaunchKernelGGL(k_zero_acc_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, reinterpret_cast<DevAccum* const*>(B->d_arena.p), R);

@@ -294,6 +294,28 @@ __global__ void __launch_bounds__(256) k_integrate_b(const RepCore* __restrict__
     integrate_body(A, d.prog);
 }
 
+// the measuring interpreter of the energy ledger (kernels_integrate.h: integrate_body<true>) and its two device-side sums, one
+// workgroup per member: the same bodies as the lone engine's kernels
+__global__ void __launch_bounds__(256) k_integrate_led_b(const RepCore* __restrict__ reps, IntDyn d) {
+    if (!reps[blockIdx.y].active) return;
+    IntArgs A = reps[blockIdx.y].in; apply_dyn(A, d, reps[blockIdx.y].draw_delta);
+    integrate_body<true>(A, d.prog);
+}
+__global__ void __launch_bounds__(64) k_ledger_ke_b(const RepCore* __restrict__ reps) {
+    const RepCore& rp = reps[blockIdx.x];
+    if (!rp.active) return;
+    ledger_ke_body(rp.in.acc, rp.in.led_part, rp.in.cm_nblocks, rp.in.led_flags);
+}
+template <typename R>
+__global__ void __launch_bounds__(64) k_ledger_pe_b(const RepNb<R>* __restrict__ rnb, const RepCore* __restrict__ reps, LedgerPe shape) {
+    const int r = blockIdx.x;
+    if (!reps[r].active) return;
+    LedgerPe L = shape;   // (the shape and lambda are the batch's; the buffers are the member's)
+    L.enb = rnb[r].nb.epart; L.eb = reps[r].bo.epart; L.ep = shape.ep ? reps[r].al.e_part : nullptr; L.jcount = reps[r].al.jcount;
+    L.e_mesh = shape.e_mesh ? rnb[r].pme.epart : nullptr; L.acc = reps[r].in.acc;
+    ledger_pe_body(L);
+}
+
 template <bool CM, bool FUSED = false>
 __global__ void __launch_bounds__(256) k_step_default_b(const RepCore* __restrict__ reps, IntDyn d) {
     if (!reps[blockIdx.y].active) return;
@@ -386,7 +408,7 @@ __global__ void k_add_work_b(DevAccum* const* __restrict__ acc, const double* __
 }
 __global__ void k_zero_acc_b(DevAccum* const* __restrict__ acc, int R) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < R && acc[r]) { DevAccum z; z.protocol_work = z.dE_last = z.heat = 0.0; z.e_slot[0] = z.e_slot[1] = z.e_slot[2] = 0.0; *acc[r] = z; }
+    if (r < R && acc[r]) { DevAccum z; z.protocol_work = z.dE_last = z.shadow_work = z.u_open = 0.0; z.heat = acc[r]->heat; z.e_slot[0] = z.e_slot[1] = z.e_slot[2] = 0.0; *acc[r] = z; }   // (heat survives a reset, as in the oracle; 0 where it is not measured)
 }
 
 template <bool CENT = false>
@@ -408,8 +430,8 @@ __global__ void __launch_bounds__(256) k_kinetic_b(const RepCore* __restrict__ r
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) ke[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-    // ... and the member's accumulators (protocol work): the Metropolis test reads them next, chain by chain
-    if (threadIdx.x < 6) ke[gridDim.x + 6 * blockIdx.x + threadIdx.x] = reinterpret_cast<const double*>(A.acc)[threadIdx.x];
+    // ... and the member's accumulators (protocol work, shadow work, heat): the Metropolis test reads them next, chain by chain
+    if (threadIdx.x < 8) ke[gridDim.x + 8 * blockIdx.x + threadIdx.x] = reinterpret_cast<const double*>(A.acc)[threadIdx.x];
 }
 
 // energy partials of every member into one slab [R][stride]: nonbonded partials | bonded partials | alchemical partials |

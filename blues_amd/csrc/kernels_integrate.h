@@ -39,7 +39,12 @@ struct Program { int n; unsigned char ops[MAX_OPS]; };
 
 struct DevAccum {
     double protocol_work, dE_last, e_slot[3], heat;
+    // the energy ledger (measure_shadow_work / measure_heat): shadow_work = sum over R of d(PE + KE) + sum over V of dKE,
+    // u_open = U(x, lambda_current) at the positions the pending R stretch started from (OP_H moves it along with lambda)
+    double shadow_work, u_open;
 };
+#define LED_HEAT 1     // IntArgs::led_flags: book the KE change of every O substep in heat
+#define LED_SHADOW 2   // ... of every V and R substep in shadow_work (the PE part: k_ledger_pe)
 
 // one packed record per cluster slot: everything the thread needs to know about its cluster arrives with a few
 // wide contiguous loads instead of a dozen dependent gathers
@@ -87,6 +92,7 @@ struct IntArgs {
     double total_mass; double* cm_part; int cm_nblocks;
     const double* mom_part; int n_mom;  // momentum partials written by k_finalize (see FinArgs)
     DevAccum* acc; double* work_trace; int trace_index;
+    double* led_part; int led_flags;   // energy ledger: [blocks][2] KE partials (heat, shadow work) of the measuring interpreter, LED_* flags
     long long* stamps;  // debug builds (-DBLUES_STAMP): cycle stamp of thread 0 at every op boundary
     Program prog;
 };
@@ -497,11 +503,22 @@ __global__ void __launch_bounds__(256) k_finalize(FinArgs A) { finalize_body<fal
 
 // `prog` is passed beside A so that the batched launch (kernels_batch.h) can hand over the shared program from its own
 // kernel arguments while A is a per-replica copy
+// KE of a cluster's real atoms, atom by atom (w = 1 / m)
+__device__ __forceinline__ double cl_kinetic(const Cluster& C) {
+    double ke = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; a++) if (a < C.na && C.w[a] > 0.0) ke += 0.5 * (C.v[a][0] * C.v[a][0] + C.v[a][1] * C.v[a][1] + C.v[a][2] * C.v[a][2]) / C.w[a];
+    return ke;
+}
+// LED: the measuring form (energy ledger).  Each thread brackets OP_V*, OP_R and OP_O with its cluster's kinetic energy; the block sums the
+// threads' totals in a fixed order into led_part[block], k_ledger_ke adds the blocks up in block order.  LED = false is the kernel as it was.
+template <bool LED = false>
 __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) {
     const int tid = threadIdx.x;
     const int cl = blockIdx.x * blockDim.x + tid;
     __shared__ double s_red[4][4];
     __shared__ double s_cm[3];
+    double led_q = 0.0, led_s = 0.0, led_k0 = 0.0;   // heat, KE part of the shadow work, KE before the op
 
     Cluster C;
     const bool active = cl < A.n_clusters;
@@ -537,17 +554,20 @@ __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) 
         case OP_V0: case OP_V1: case OP_V2: {
             if (active) {
                 double F[4][3];
+                if constexpr (LED) led_k0 = cl_kinetic(C);
                 load_force(A, C, op - OP_V0, F);
 #pragma unroll
                 for (int a = 0; a < 4; a++)
 #pragma unroll
                     for (int k = 0; k < 3; k++) C.v[a][k] += A.hV * F[a][k] * C.w[a];
                 rattle(C, A.tol, A);
+                if constexpr (LED) led_s += cl_kinetic(C) - led_k0;
             }
         } break;
         case OP_R: {
             if (active) {
                 double xr[4][3], x1[4][3];
+                if constexpr (LED) led_k0 = cl_kinetic(C);
 #pragma unroll
                 for (int a = 0; a < 4; a++) for (int k = 0; k < 3; k++) {
                     xr[a][k] = C.x[a][k];
@@ -559,6 +579,7 @@ __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) 
                 for (int a = 0; a < 4; a++) if (a < C.na) for (int k = 0; k < 3; k++) C.v[a][k] += (C.x[a][k] - x1[a][k]) * A.inv_hR;
                 rattle(C, A.tol, A);
                 moved = true;
+                if constexpr (LED) led_s += cl_kinetic(C) - led_k0;
             }
         } break;
         case OP_A0: case OP_A1: case OP_A2: {
@@ -580,6 +601,7 @@ __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) 
         } break;
         case OP_O: {
             if (active) {
+                if constexpr (LED) led_k0 = cl_kinetic(C);
 #pragma unroll
                 for (int a = 0; a < 4; a++) if (a < C.na) {
                     double g[3];
@@ -592,6 +614,7 @@ __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) 
                     for (int k = 0; k < 3; k++) C.v[a][k] = A.aO * C.v[a][k] + A.bO * s * g[k];
                 }
                 rattle(C, A.tol, A);
+                if constexpr (LED) led_q += cl_kinetic(C) - led_k0;
             }
             draw++;
         } break;
@@ -631,6 +654,7 @@ __device__ __forceinline__ void integrate_body(IntArgs& A, const Program& prog) 
                 const int s = op - OP_H01;
                 const double dE = A.acc->e_slot[s + 1] - A.acc->e_slot[s];
                 A.acc->protocol_work += dE; A.acc->dE_last = dE;
+                if constexpr (LED) A.acc->u_open += dE;   // U(x, lambda) of the open stretch follows lambda: the positions are the ones the slots were formed at
             }
         } break;
         case OP_END: {
@@ -683,6 +707,19 @@ _Pragma("unroll") for (int a = 0; a < 4; a++) if (a < C.na) for (int k = 0; k < 
 #ifdef BLUES_STAMP
     if (cl == 0 && A.stamps) A.stamps[1 + prog.n] = clock64();
 #endif
+    if constexpr (LED) {   // this block's KE partials: lanes by wave_sum, waves in wave order (inactive threads carry 0)
+        if (!(A.led_flags & LED_HEAT)) led_q = 0.0;
+        if (!(A.led_flags & LED_SHADOW)) led_s = 0.0;
+        led_q = wave_sum(led_q); led_s = wave_sum(led_s);
+        __syncthreads();   // (s_red may still be read by the last CM op)
+        if ((tid & 63) == 0) { s_red[tid >> 6][0] = led_q; s_red[tid >> 6][1] = led_s; }
+        __syncthreads();
+        if (tid < 2) {
+            double t = 0.0;
+            for (int w = 0; w < (int)((blockDim.x + 63) >> 6); w++) t += s_red[w][tid];
+            A.led_part[blockIdx.x * 2 + tid] = t;
+        }
+    }
     if (!active) return;
     // ---- write back, refresh the fixed-point image, check list validity
     bool need_rebuild = false, bad = false;
@@ -717,6 +754,84 @@ _Pragma("unroll") for (int a = 0; a < 4; a++) if (a < C.na) for (int k = 0; k < 
 }
 
 __global__ void __launch_bounds__(256) k_integrate(IntArgs A) { integrate_body(A, A.prog); }
+__global__ void __launch_bounds__(256) k_integrate_led(IntArgs A) { integrate_body<true>(A, A.prog); }
+
+// ---- energy ledger: the device-side sums.  One workgroup of 64 threads per chain; no atomics, every sum in a fixed order.
+// k_ledger_ke: the blocks' KE partials of the launch before, in block order, into heat and shadow_work.
+__device__ __forceinline__ void ledger_ke_body(DevAccum* acc, const double* __restrict__ part, int nblocks, int flags) {
+    if (threadIdx.x != 0) return;
+    double q = 0.0, s = 0.0;
+    for (int b = 0; b < nblocks; b++) { q += part[2 * b]; s += part[2 * b + 1]; }
+    if (flags & LED_HEAT) acc->heat += q;
+    if (flags & LED_SHADOW) acc->shadow_work += s;
+}
+__global__ void __launch_bounds__(64) k_ledger_ke(DevAccum* acc, const double* part, int nblocks, int flags) { ledger_ke_body(acc, part, nblocks, flags); }
+
+// k_ledger_pe: the potential energy of an energy-form pass from its partials, in the order the host uses (energy_sum, energy_totals:
+// partial by partial, then term by term) -- without the constants that cancel in a difference at fixed frozen atoms and box (frozen-frozen
+// pairs, Ewald self term, dispersion correction).  close = 0: u_open = U (a stretch of R substeps starts here);
+// close = 1: shadow_work += U - u_open, u_open = U (the stretch ends here, the next one starts at the same positions).
+struct LedgerPe {
+    const double* enb; const double* eb; const double* ep; const int* jcount; const double* e_mesh;   // partials: nonbonded, bonded [nbb][T_NTYPES], alchemical [blocks][K2_NP]; null: none
+    int nw, nbb, PA, k2_jiter, k2_nblocks_env;
+    double le;   // lambda_electrostatics the alchemical kernel ran slot 0 with
+    DevAccum* acc; int close;
+};
+__device__ __forceinline__ double ledger_serial_sum(const double* __restrict__ p, int n, int stride) {   // p[0] + p[stride] + ... in order, 8 loads in flight
+    double s = 0.0;
+    for (int i = 0; i < n; i += 8) {
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) t[u] = i + u < n ? p[(size_t)(i + u) * stride] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; u++) if (i + u < n) s += t[u];
+    }
+    return s;
+}
+__device__ __forceinline__ void ledger_pe_body(const LedgerPe& L) {
+    __shared__ double s_t[16];
+    const int tid = threadIdx.x;
+    // thread 0: nonbonded (pairs of partials, as the host adds them); 1..6: the bonded kinds; 8..13: the alchemical sums
+    if (tid == 0) {
+        double e = 0.0;
+        for (int w = 0; w < L.nw; w += 8) {
+            double t[8][2];
+#pragma unroll
+            for (int u = 0; u < 8; u++) { t[u][0] = w + u < L.nw ? L.enb[2 * (w + u)] : 0.0; t[u][1] = w + u < L.nw ? L.enb[2 * (w + u) + 1] : 0.0; }
+#pragma unroll
+            for (int u = 0; u < 8; u++) if (w + u < L.nw) e += t[u][0] + t[u][1];
+        }
+        s_t[0] = e;
+    } else if (tid >= 1 && tid <= T_NTYPES) {
+        s_t[tid] = L.nbb > 0 ? ledger_serial_sum(L.eb + (tid - 1), L.nbb, T_NTYPES) : 0.0;
+    } else if (tid >= 8 && tid < 8 + K2_NE) {
+        double s = 0.0;
+        if (L.ep) {
+            const int nb_env = k2_env_blocks(*L.jcount, L.PA, L.k2_jiter), q = tid - 8;
+            s = ledger_serial_sum(L.ep + q, min(nb_env, L.k2_nblocks_env), K2_NP);
+            s += L.ep[(size_t)L.k2_nblocks_env * K2_NP + q];
+        }
+        s_t[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double T[10];
+    T[0] = s_t[1 + T_BOND]; T[1] = s_t[1 + T_ANGLE]; T[2] = s_t[1 + T_TORSION]; T[3] = s_t[0]; T[4] = s_t[1 + T_EXC];
+    T[5] = L.ep ? s_t[8 + 1] + s_t[8 + 4] : 0.0; T[6] = L.ep ? L.le * s_t[8 + 0] + s_t[8 + 5] : 0.0;
+    T[7] = s_t[1 + T_RESTR]; T[8] = s_t[1 + T_EWEX] + (L.e_mesh ? *L.e_mesh : 0.0); T[9] = 0.0;
+    double U = 0.0;
+#pragma unroll
+    for (int t = 0; t < 10; t++) U += T[t];
+    if (L.close) L.acc->shadow_work += U - L.acc->u_open;
+    L.acc->u_open = U;
+}
+__global__ void __launch_bounds__(64) k_ledger_pe(LedgerPe L) { ledger_pe_body(L); }
+// blues_reset / the first-step block of a measuring engine: the work and the slots go, heat stays (and shadow_work unless asked), as the
+// oracle's orc_reset / first-step block leave them
+__global__ void k_ledger_reset(DevAccum* acc, int zero_shadow) {
+    acc->protocol_work = 0.0; acc->dE_last = 0.0; acc->e_slot[0] = acc->e_slot[1] = acc->e_slot[2] = 0.0; acc->u_open = 0.0;
+    if (zero_shadow) acc->shadow_work = 0.0;
+}
 
 // ---- state transfer (setPositions / State snapshots): new positions arrive either interleaved from the host
 // ([n][3], stride 3) or as a device-resident snapshot (SoA, stride 1).  One pass writes the master positions, refreshes

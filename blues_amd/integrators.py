@@ -36,8 +36,6 @@ class AlchemicalExternalLangevinIntegrator(object):
     def __init__(self, alchemical_functions, splitting="R V O H O V R", temperature=298.0, collision_rate=1.0,
                  timestep=0.001, constraint_tolerance=1e-8, measure_shadow_work=False, measure_heat=True,
                  nsteps_neq=100, nprop=1, prop_lambda=0.3, seed=0, *args, **kwargs):
-        if measure_shadow_work:
-            raise NotImplementedError("measure_shadow_work=True is not supported (BLUES never enables it)")
         self._alchemical_functions = dict(alchemical_functions)
         unknown = set(self._alchemical_functions) - {"lambda_sterics", "lambda_electrostatics"}
         if unknown:
@@ -51,6 +49,10 @@ class AlchemicalExternalLangevinIntegrator(object):
         self._collision_rate = unit.value_in(collision_rate, "1/picosecond")
         self._timestep = unit.value_in(timestep, "picosecond")
         self._constraint_tolerance = float(constraint_tolerance)
+        # The engine measures on request only: with measure_shadow_work it books the shadow work on the device, and the heat too iff
+        # measure_heat.  Without it neither flag is sent -- measure_heat=True is the reference's default and nothing in BLUES reads
+        # `heat`, so the default path does not pay for it (heat alone: IntegratorData(measure_heat=1)).
+        self._measure_shadow_work = bool(measure_shadow_work)
         self._measure_heat = measure_heat
         self._n_steps_neq = int(nsteps_neq)
         self._n_lambda_steps = self._n_steps_neq * tokens.count("H")
@@ -87,7 +89,9 @@ class AlchemicalExternalLangevinIntegrator(object):
                               lambda_sterics=np.array(ls), lambda_electrostatics=np.array(le), splitting=self._splitting,
                               collision_rate=self._collision_rate, nprop=self._nprop, prop_lambda_min=self._prop_lambda[0],
                               prop_lambda_max=self._prop_lambda[1], constraint_tolerance=self._constraint_tolerance,
-                              seed=self._seed, replica=replica, precision=precision)
+                              seed=self._seed, replica=replica, precision=precision,
+                              measure_shadow_work=int(self._measure_shadow_work),
+                              measure_heat=int(self._measure_shadow_work and bool(self._measure_heat)))
 
     # ---- engine-backed calls
     def _bind(self, engine):
@@ -146,7 +150,8 @@ def generateNCMCIntegrator(nstepsNC=None, alchemical_functions=None, splitting="
         alchemical_functions = dict(DEFAULT_ALCHEMICAL_FUNCTIONS)
     return AlchemicalExternalLangevinIntegrator(
         alchemical_functions=alchemical_functions, splitting=splitting, temperature=temperature, nsteps_neq=nstepsNC,
-        timestep=dt, nprop=nprop, prop_lambda=propLambda, seed=kwargs.get("seed", 0))
+        timestep=dt, nprop=nprop, prop_lambda=propLambda, seed=kwargs.get("seed", 0),
+        measure_shadow_work=kwargs.get("measure_shadow_work", False), measure_heat=kwargs.get("measure_heat", True))
 
 
 class LangevinIntegrator(object):

@@ -70,7 +70,10 @@ def metropolis(chain, unmodified_at_x1=None, correction=None):
     unmodified_at_x1: the `alch` context's energy at the switched coordinates where a batch has evaluated it for all chains.
     correction: the correction itself where a batch has formed it as a differential (BatchedBLUESSimulation._decide_batched)."""
     integrator = chain._ncmc_sim.context._integrator
+    # -(protocol_work + shadow_work) / kT: the shadow work is the engine's measured one where the integrator was built with
+    # measure_shadow_work=True (0 otherwise).  In a batch both globals come out of the accumulators the batch read back for all chains.
     log_p = integrator.getLogAcceptanceProbability(chain._ncmc_sim.context)
+    work_ncmc = float(log_p)
     log_u = math.log(chain._rng.random_sample())
     given, correction = correction, 0.0
     if not np.isnan(log_p):       # a NaN work rejects without asking for energies (the reference's guard)
@@ -78,7 +81,7 @@ def metropolis(chain, unmodified_at_x1=None, correction=None):
         logger.debug('NCMCLogAcceptanceProbability = %.6f + Alchemical Correction = %.6f' % (log_p, correction))
         log_p = log_p + correction
     return {'accept': bool(log_p > log_u), 'log_accept': float(log_p), 'correction': float(correction), 'randnum': log_u,
-            'protocol_work': integrator.getGlobalVariableByName('protocol_work')}
+            'protocol_work': integrator.getGlobalVariableByName('protocol_work'), 'work_ncmc': work_ncmc}
 
 
 def record_decision(chain, decision):

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define BLUES_ABI_VERSION 8
+#define BLUES_ABI_VERSION 9
 
 /* nonbonded_method */
 #define BLUES_NB_NOCUTOFF 0   /* vacuum: every pair, bare Coulomb, no periodicity; the box is stored and has no effect */
@@ -155,6 +155,18 @@ typedef struct BluesIntegratorDesc {
      * for direction 'insert', 1 - i / nsteps_neq for 'delete' (evaluated by the host language).  Work is kept in kJ/mol. */
     int32_t switching_mode;
     int32_t steps_per_propagation;
+    /* ABI 9: measure_shadow_work / measure_heat of AlchemicalExternalLangevinIntegrator.__init__ (reference blues/integrators.py:98-121).
+     * BLUES_SWITCH_NONE only: blues_engine_create refuses either flag with a switching mode (the velocity-Verlet integrator keeps its
+     * own shadow work).  Both 0: the engine launches what it launched before ABI 9, and both globals read 0.  Otherwise the engine
+     * steps through its general step interpreter and books, on the device,
+     *   heat        += KE after the velocity constraints - KE before, over every O substep;
+     *   shadow_work += change of PE + KE across every R substep (its SHAKE and RATTLE included) and of KE across every V substep
+     *                  (its RATTLE included).
+     * Nothing is booked for the first-step block, the CMMotionRemover, H, or an instantaneous Move (that work stays in protocol_work).
+     * Over any stretch of a switch, with E = potential + kinetic energy (blues_get_energy):
+     *   dE = d protocol_work + d shadow_work + d heat + sum of the kinetic energy the CMMotionRemover took. */
+    int32_t measure_shadow_work;
+    int32_t measure_heat;
 } BluesIntegratorDesc;
 #define BLUES_SWITCH_NONE 0
 #define BLUES_SWITCH_VV 1
@@ -278,6 +290,8 @@ int blues_run_switch(BluesEngine *h, int32_t n_steps, double *work_trace /* [n_s
  * names: lambda step lambda_step n_lambda_steps nsteps protocol_work shadow_work
  *        perturbed_pe unperturbed_pe first_step nprop prop prop_lambda_min
  *        prop_lambda_max Eold Enew heat kT lambda_sterics lambda_electrostatics
+ *        (shadow_work and heat: measured and settable where the integrator's measure_* flag is set, 0 and
+ *        not settable otherwise; blues_reset zeroes shadow_work and leaves heat, as it does the reference's)
  *        and, with a switching_mode: total_work Epert initial_energy final_energy
  *        accept naccept ntrials psteps (reference blues/switching.py:1062-1080; kJ/mol) */
 int blues_get_global(BluesEngine *h, const char *name, double *value);
