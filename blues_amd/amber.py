@@ -223,16 +223,26 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
         else:
             bond_atoms.append((i, j)); bond_params.append((r0, k))
     angle_atoms, angle_params = [], []
+    bond_dist = {frozenset(p_): d for p_, d in zip(cons_atoms, cons_dist)}   # (the constrained bonds; the 1-3 constraints below are not bonds)
+
+    def constrain_13(i, j, k_, th0):
+        """the 1-3 distance that the constrained bonds i-j, k-j and the equilibrium angle fix, once per pair"""
+        pair = (min(i, k_), max(i, k_))
+        if pair not in constrained_pair:
+            d_ij, d_kj = bond_dist[frozenset((i, j))], bond_dist[frozenset((k_, j))]
+            cons_atoms.append((i, k_)); cons_dist.append(float(np.sqrt(d_ij ** 2 + d_kj ** 2 - 2 * d_ij * d_kj * np.cos(th0))))
+            constrained_pair.add(pair)
+
     for a in angles:
         i, j, k_, t = int(a[0]) // 3, int(a[1]) // 3, int(a[2]) // 3, int(a[3]) - 1
         th0, kk = at[t], 2.0 * ak[t] * KCAL
         if rigid_water and is_water[i] and is_water[j] and is_water[k_]:
-            pair = (min(i, k_), max(i, k_))
-            if pair not in constrained_pair:  # H-H distance from the two O-H bonds and the angle
-                d_ij = next(d for (p_, d) in zip(cons_atoms, cons_dist) if set(p_) == {i, j})
-                d_kj = next(d for (p_, d) in zip(cons_atoms, cons_dist) if set(p_) == {k_, j})
-                cons_atoms.append((i, k_)); cons_dist.append(float(np.sqrt(d_ij ** 2 + d_kj ** 2 - 2 * d_ij * d_kj * np.cos(th0))))
-                constrained_pair.add(pair)
+            constrain_13(i, j, k_, th0)  # H-H distance from the two O-H bonds and the angle
+            continue
+        # HAngles (OpenMM): on top of AllBonds, every angle H-X-H and every angle H-O-X becomes the 1-3 distance that the two bond
+        # lengths and the equilibrium angle fix, and leaves the harmonic terms; hydrogens by atomic number (repartitioned masses hide them)
+        if constraints == "HAngles" and ((atnum[i] == 1 and atnum[k_] == 1) or (atnum[j] == 8 and (atnum[i] == 1 or atnum[k_] == 1))):
+            constrain_13(i, j, k_, th0)
             continue
         angle_atoms.append((i, j, k_)); angle_params.append((th0, kk))
     tors_atoms, tors_params = [], []

@@ -332,6 +332,12 @@ struct BluesEngine {
     DBuf<int> d_alch_orig, d_alch_local, d_exc_start, d_exc_partner; DBuf<double> d_exc_params;
     DBuf<int> d_cl_atoms, d_cl_type, d_cl_nc, d_cl_alch, d_cl_mobile, d_cl_sorted; DBuf<double> d_cl_dist;
     DBuf<ClusterRec> d_recs; std::vector<ClusterRec> h_recs;
+    // general constraint clusters (kernels_constraints.h): tables of their own beside the <= 4-atom clusters
+    std::vector<GenCluster> gen_h; std::vector<GenAtom> gen_atoms_h; std::vector<GenCons> gen_cons_h;
+    std::vector<int> gen_tree;   // (atom, the atom it is constrained to) in breadth-first order, cluster by cluster: how a cluster is made one periodic image
+    DBuf<GenCluster> d_gen; DBuf<GenAtom> d_gen_atoms; DBuf<GenCons> d_gen_cons;
+    int n_gen() const { return (int)gen_h.size(); }
+    int gen_blocks() const { const int wpb = int_threads / 64; return (n_gen() + wpb - 1) / wpb; }
     DBuf<AlchJRec> d_jrec; DBuf<AlchARec> d_arec;
     DBuf<double> d_mom_part; bool vel_clean = false, pass_valid_for_l = true;  // velocities unchanged since the last force pass (momentum partials valid)
     DBuf<FinRec> d_finrecs; std::vector<int> h_row_of_orig, h_row_start;
@@ -621,6 +627,8 @@ static int build_clusters(BluesEngine* h, const BluesSystemDesc* s) {
     for (size_t c = 0; c < cons.size(); c++) by_root[find(cons[c].first)].push_back((int)c);
     std::vector<char> in_cluster(n, 0);
     std::vector<HostCluster> alch_first, rest;
+    std::vector<int> gen_mi;
+    h->gen_h.clear(); h->gen_atoms_h.clear(); h->gen_cons_h.clear(); h->gen_tree.clear();
     auto push = [&](const HostCluster& hc) {
         bool is_alch = false;
         for (int a = 0; a < 4; a++) if (hc.atoms[a] >= 0 && h->T->alch_local[hc.atoms[a]] >= 0) is_alch = true;
@@ -629,10 +637,60 @@ static int build_clusters(BluesEngine* h, const BluesSystemDesc* s) {
     for (auto& kv : by_root) {
         const std::vector<int>& cl = kv.second;
         HostCluster hc; for (int a = 0; a < 4; a++) hc.atoms[a] = -1; hc.dist[0] = hc.dist[1] = hc.dist[2] = 0; hc.nc = (int)cl.size();
-        if (cl.size() > 3) E_FAIL(h, "constraint cluster with %zu constraints is not supported (HBonds / rigid water only)", cl.size());
         std::vector<int> atoms;
         for (int c : cl) for (int a : {cons[c].first, cons[c].second}) if (std::find(atoms.begin(), atoms.end(), a) == atoms.end()) atoms.push_back(a);
-        if (atoms.size() > 4) E_FAIL(h, "constraint cluster with %zu atoms is not supported", atoms.size());
+        bool general = cl.size() > 3 || atoms.size() > 4;
+        if (!general && !(cl.size() == 3 && atoms.size() == 3) && cl.size() > 1) {   // neither a triangle nor a star: no common centre
+            general = true;
+            for (int cand : {cons[cl[0]].first, cons[cl[0]].second}) {
+                bool all = true;
+                for (int c : cl) if (cons[c].first != cand && cons[c].second != cand) all = false;
+                if (all) general = false;
+            }
+        }
+        if (general) {   // a general cluster (kernels_constraints.h): atoms in order of first appearance, constraints in list order, coloured
+            if (atoms.size() > GEN_MAX_ATOMS || cl.size() > GEN_MAX_CONS)
+                E_FAIL(h, "constraint cluster with %zu atoms and %zu constraints exceeds the capacity of a general constraint cluster (%d atoms, %d constraints): "
+                          "constraints this far-reaching (a whole protein under AllBonds) are not supported", atoms.size(), cl.size(), GEN_MAX_ATOMS, GEN_MAX_CONS);
+            if (h->led_flags) E_FAIL(h, "measure_shadow_work / measure_heat are not supported on a System with general constraint clusters (%zu atoms, %zu constraints)", atoms.size(), cl.size());
+            if (gen_mi.empty()) { gen_mi.assign(n, 0); for (size_t m = 0; m < h->mobile.size(); m++) gen_mi[h->mobile[m]] = (int)m; }
+            GenCluster G; memset(&G, 0, sizeof G);
+            G.a0 = (int)h->gen_atoms_h.size(); G.na = (int)atoms.size(); G.c0 = (int)h->gen_cons_h.size(); G.nc = (int)cl.size();
+            std::map<int, int> local;
+            for (size_t a = 0; a < atoms.size(); a++) {
+                GenAtom R; memset(&R, 0, sizeof R);
+                R.atom = atoms[a]; R.sorted = 0; R.mobile = gen_mi[atoms[a]]; R.alch = h->T->alch_local[atoms[a]]; R.islot = -1; R.w = 1.0 / h->T->mass[atoms[a]];
+                h->gen_atoms_h.push_back(R); local[atoms[a]] = (int)a; in_cluster[atoms[a]] = 1;
+            }
+            // greedy colouring: constraints in list order, the lowest colour no constraint at either atom has taken
+            std::vector<unsigned> used(atoms.size(), 0u); std::vector<int> colour(cl.size());
+            int ncol = 0;
+            for (size_t q = 0; q < cl.size(); q++) {
+                const int i = local[cons[cl[q]].first], j = local[cons[cl[q]].second];
+                const unsigned taken = used[i] | used[j];
+                int c = 0; while (c < 32 && ((taken >> c) & 1u)) c++;
+                if (c >= GEN_MAX_COLOURS) E_FAIL(h, "constraint cluster with %zu atoms and %zu constraints needs more than %d colours (an atom with too many constraints)", atoms.size(), cl.size(), GEN_MAX_COLOURS);
+                colour[q] = c; used[i] |= 1u << c; used[j] |= 1u << c; ncol = std::max(ncol, c + 1);
+            }
+            G.ncol = ncol;
+            for (int c = 0; c < ncol; c++) {
+                G.col[c] = (int)h->gen_cons_h.size() - G.c0;
+                for (size_t q = 0; q < cl.size(); q++) if (colour[q] == c) {
+                    GenCons K; K.i = local[cons[cl[q]].first]; K.j = local[cons[cl[q]].second]; K.d2 = cdist[cl[q]] * cdist[cl[q]];
+                    h->gen_cons_h.push_back(K);
+                }
+            }
+            for (int c = ncol; c <= GEN_MAX_COLOURS; c++) G.col[c] = G.nc;
+            // breadth-first tree over the constraints from the first atom
+            { std::vector<char> seen(atoms.size(), 0); std::vector<int> queue(1, 0); seen[0] = 1;
+              for (size_t qh = 0; qh < queue.size(); qh++) for (int c : cl) {
+                  const int i = local[cons[c].first], j = local[cons[c].second];
+                  const int other = i == queue[qh] ? j : (j == queue[qh] ? i : -1);
+                  if (other >= 0 && !seen[other]) { seen[other] = 1; queue.push_back(other); h->gen_tree.push_back(atoms[other]); h->gen_tree.push_back(atoms[queue[qh]]); }
+              } }
+            h->gen_h.push_back(G);
+            continue;
+        }
         if (cl.size() == 3 && atoms.size() == 3) {  // triangle: canonical order (0,1),(0,2),(1,2)
             int a = cons[cl[0]].first, b = cons[cl[0]].second, c2a = cons[cl[1]].first, c2b = cons[cl[1]].second;
             int shared, other1, third;
@@ -719,7 +777,11 @@ static int build_clusters(BluesEngine* h, const BluesSystemDesc* s) {
     }
     h->int_threads = ncl <= 256 ? std::max(128, ((ncl + 63) / 64) * 64) : 256;
     h->int_blocks = std::max(1, (ncl + h->int_threads - 1) / h->int_threads);
-    h->d_cm_part.alloc((size_t)h->int_blocks * 3);
+    h->d_cm_part.alloc((size_t)(h->int_blocks + h->n_gen()) * 3);   // (general clusters: one entry each behind the blocks')
+    if (h->n_gen()) {
+        h->fast_step = false;   // the general interpreter and k_finalize, as a measuring engine: no fused step kernel knows a general cluster
+        h->d_gen.upload(h->gen_h); h->d_gen_atoms.upload(h->gen_atoms_h); h->d_gen_cons.upload(h->gen_cons_h);
+    }
     if (h->led_flags) h->d_led_part.alloc((size_t)h->int_blocks * 2);
     return 0;
 }
@@ -862,6 +924,7 @@ static int nocut_layout(BluesEngine* h) {
               h->h_recs[c].e0[a] = row >= 0 ? h->h_row_start[row] : 0; h->h_recs[c].e1[a] = row >= 0 ? h->h_row_start[row + 1] : 0;
           }
           h->d_recs.upload(h->h_recs); }
+        if (h->n_gen()) { for (GenAtom& R : h->gen_atoms_h) { R.sorted = R.atom; R.islot = islot[R.atom]; } h->d_gen_atoms.upload(h->gen_atoms_h); }
         { std::vector<AlchJRec> jr(env.size());
           for (size_t q = 0; q < env.size(); q++) { const int j = env[q]; jr[q].jo = j; jr[q].jsrt = j | (h->T->mass[j] != 0.0 ? (1 << 30) : 0); jr[q].sig = h->T->sigma[j]; jr[q].eps = std::sqrt(h->T->eps[j]); jr[q].q = h->T->charge[j]; }
           if (jr.empty()) jr.resize(1);
@@ -999,6 +1062,7 @@ static int sort_and_tile(BluesEngine* h) {
         // with its own register / LDS budget, sub-tile nonbonded variant) win -- measured 259 vs 197 us at R = 64.
         h->fuse_forces = nit * h->batch_R <= 32;
         if (h->tune.fuse_forces >= 0) h->fuse_forces = h->tune.fuse_forces != 0;
+        if (h->n_gen()) h->fuse_forces = false;   // (general constraint clusters: the decomposed force pass and k_finalize only)
         if (h->fuse_forces) { WPB = 4; NW = std::max(4, NW / 3); }  // ~3 segments per wave: as long as the alchemical role
         NW = std::max(WPB, (NW / WPB) * WPB);
         if (h->pin_jcap > 0 && h->batch && std::min<double>(n, est / 1.8 * 1.2) + 64 <= h->pin_jcap) { jcap = h->pin_jcap; h->jcap = jcap; CH = h->pin_seg; NW = h->pin_nw; WPB = h->pin_wpb; }
@@ -1180,6 +1244,7 @@ static int sort_and_tile(BluesEngine* h) {
               h->h_recs[c].e0[a] = row >= 0 ? h->h_row_start[row] : 0; h->h_recs[c].e1[a] = row >= 0 ? h->h_row_start[row + 1] : 0;
           }
           h->d_recs.upload(h->h_recs); }
+        if (h->n_gen()) { for (GenAtom& R : h->gen_atoms_h) { R.sorted = h->h_sorted_of_orig[R.atom]; R.islot = islot[R.atom]; } h->d_gen_atoms.upload(h->gen_atoms_h); }
         h->d_tile_atoms.upload(tile_atoms); h->d_islot.upload(islot);
         h->d_ex_start.upload(ex_start); h->d_ex_idx.upload(ex_idx);
         h->d_jrec.alloc((size_t)jcap);
@@ -1321,6 +1386,7 @@ static IntArgs make_int_args(BluesEngine* h) {
     IntArgs A; memset(&A, 0, sizeof A);
     A.n = h->n; A.n_clusters = (int)h->clusters.size();
     A.recs = h->d_recs.p;
+    if (h->n_gen()) { A.gen = h->d_gen.p; A.gen_atoms = h->d_gen_atoms.p; A.gen_cons = h->d_gen_cons.p; A.n_gen = h->n_gen(); A.gen_block0 = h->int_blocks; }
     for (int k = 0; k < 3; k++) { A.x[k] = h->d_x[k].p; A.v[k] = h->d_v[k].p; A.xbuild[k] = h->d_xbuild[k].p; }
     A.mass = h->d_mass.p;
     A.ftot = h->d_ftot.p; A.alch_self = h->d_alch_self.p;
@@ -1344,7 +1410,7 @@ static IntArgs make_int_args(BluesEngine* h) {
     for (int k = 0; k < 3; k++) { A.xprune[k] = pruned ? h->d_xprune[k].p : nullptr; A.fscale[k] = (float)(h->box[k] / 4294967296.0); }
     A.pneed = pruned ? h->d_pneed.p : nullptr;
     A.prune_trig2 = (float)(h->ptrig * h->ptrig);
-    A.total_mass = h->total_mass; A.cm_part = h->d_cm_part.p; A.cm_nblocks = h->int_blocks;
+    A.total_mass = h->total_mass; A.cm_part = h->d_cm_part.p; A.cm_nblocks = h->int_blocks + h->n_gen();
     A.mom_part = h->d_mom_part.p; A.n_mom = h->n_islots / 64 + 2;
     A.acc = h->d_acc.p; A.work_trace = h->tracing ? h->d_trace.p : nullptr; A.trace_index = h->prog_trace;
     A.led_part = h->d_led_part.p; A.led_flags = h->led_flags;
@@ -1365,7 +1431,7 @@ static int flush_program(BluesEngine* h) {
     static const unsigned char P_MD_NC[1] = {OP_L};
     bool has_part = false;
     for (int q = 0; q < h->prog.n; q++) has_part |= h->prog.ops[q] == OP_CM_PART;
-    const dim3 grid(h->int_blocks, batch_lead(h) ? h->batch->R() : 1), block(h->int_threads);
+    const dim3 grid(h->int_blocks + h->gen_blocks(), batch_lead(h) ? h->batch->R() : 1), block(h->int_threads);   // (general clusters: their workgroups at the tail of the grid)
     IntDyn D; D.draw_base = A.draw_base; D.noise_draw_base = A.noise_draw_base; D.n_noise = A.n_noise; D.trace_index = A.trace_index; D.tracing = A.work_trace != nullptr; D.prog = A.prog;
     for (int s3 = 0; s3 < 3; s3++) D.fin_le[s3] = h->fin_le[s3];
     D.fin_mask = h->fin_mask;
@@ -1391,10 +1457,15 @@ static int flush_program(BluesEngine* h) {
         else if (!dry) hipLaunchKernelGGL(k_step_md<false>, grid, block, 0, h->cur, A);
     } else {
         if (has_part) E_FAIL(h, "internal: OP_CM_PART outside a specialised program");
+        if (h->n_gen() && (h->led_flags || h->fast_step)) E_FAIL(h, "internal: an engine with general constraint clusters outside the general interpreter");
         if (h->led_flags) {   // the measuring interpreter, then the blocks' KE partials in block order (energy ledger)
             if (lead) { hipLaunchKernelGGL(k_integrate_led_b, grid, block, 0, h->cur, reps, D); hipLaunchKernelGGL(k_ledger_ke_b, dim3(h->batch->R()), dim3(64), 0, h->cur, reps); }
             else if (!dry) { hipLaunchKernelGGL(k_integrate_led, grid, block, 0, h->cur, A); hipLaunchKernelGGL(k_ledger_ke, dim3(1), dim3(64), 0, h->cur, h->d_acc.p, h->d_led_part.p, h->int_blocks, h->led_flags); }
             h->st_launches++;
+        }
+        else if (h->n_gen()) {
+            if (lead) hipLaunchKernelGGL(k_integrate_gen_b, grid, block, 0, h->cur, reps, D);
+            else if (!dry) hipLaunchKernelGGL(k_integrate_gen, grid, block, 0, h->cur, A);
         }
         else if (lead) hipLaunchKernelGGL(k_integrate_b, grid, block, 0, h->cur, reps, D);
         else if (!dry) hipLaunchKernelGGL(k_integrate, grid, block, 0, h->cur, A);
@@ -2129,6 +2200,9 @@ static int force_pass(BluesEngine* h, int base_L) {
     if ((h->n_cent > 0 || h->pair_mode != BLUES_PAIR_STANDARD) && (h->k1_mode != 4 || h->fuse_forces || h->k2_dense))
         E_FAIL(h, "internal: an engine with custom forces left the decomposed NoCutoff path (k1_mode %d, fuse_forces %d, k2_dense %d)", h->k1_mode, (int)h->fuse_forces, (int)h->k2_dense);
 
+    if (h->n_gen() && (h->fast_step || h->fuse_forces || fin_fusable(h)))
+        E_FAIL(h, "internal: an engine with general constraint clusters was laid out for a fused kernel (fast_step %d, fuse_forces %d)", (int)h->fast_step, (int)h->fuse_forces);
+
     // ---- which schedule (BluesTuning.fork; every one of them computes the same bits)
     const int fork_mode = h->batch ? h->batch->tune.fork : h->tune.fork;
     const bool fused = h->fuse_forces && h->wpb == 4;   // (one launch with the nonbonded, alchemical and bonded roles: nothing to fork)
@@ -2497,7 +2571,7 @@ static int emit_cm(BluesEngine* h) {
         const bool md_head = h->prog.n == 0 && h->split == "L" && !h->tracing;
         if (after_finish || md_head) return emit(h, OP_CM_PART);
     }
-    if (h->int_blocks == 1) return emit(h, OP_CM_BLOCK);
+    if (h->int_blocks == 1 && h->n_gen() == 0) return emit(h, OP_CM_BLOCK);   // (general clusters add their momenta as entries of their own: the two-launch form)
     if (emit(h, OP_CM_REDUCE)) return 1;
     if (flush_program(h)) return 1;
     return emit(h, OP_CM_APPLY);
@@ -2755,6 +2829,9 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
     // (not the box: a MonteCarloBarostat leaves every member in its own; margins, fixed-point scales and PME tables are per member in the records)
 #undef BC
     if (a->clusters.size() != b->clusters.size()) { *why = "constraint clusters"; return false; }
+    if (a->gen_h.size() != b->gen_h.size() || a->gen_tree != b->gen_tree || a->gen_cons_h.size() != b->gen_cons_h.size()) { *why = "general constraint clusters"; return false; }
+    for (size_t g = 0; g < a->gen_h.size(); g++) if (memcmp(&a->gen_h[g], &b->gen_h[g], sizeof(GenCluster))) { *why = "general constraint clusters"; return false; }
+    for (size_t c = 0; c < a->gen_cons_h.size(); c++) if (a->gen_cons_h[c].i != b->gen_cons_h[c].i || a->gen_cons_h[c].j != b->gen_cons_h[c].j) { *why = "general constraint clusters"; return false; }
     if (a->mobile != b->mobile) { *why = "mobile atoms"; return false; }
     if (a->alch != b->alch) { *why = "alchemical atoms"; return false; }
     if (a->tab_ls != b->tab_ls || a->tab_le != b->tab_le) { *why = "lambda schedule"; return false; }
@@ -3640,6 +3717,11 @@ int blues_set_positions(BluesEngine* h, const double* xyz, int32_t n_atoms) {
             double d = st[3 * c.atoms[a] + k] - st[3 * c.atoms[0] + k];
             st[3 * c.atoms[a] + k] -= lattice_shift(h, k, d);
         }
+    for (size_t q = 0; q < h->gen_tree.size(); q += 2)   // general clusters: every atom beside the one it is constrained to, from the first atom outwards
+        for (int k = 0; k < 3; k++) {
+            const double d = st[3 * h->gen_tree[q] + k] - st[3 * h->gen_tree[q + 1] + k];
+            st[3 * h->gen_tree[q] + k] -= lattice_shift(h, k, d);
+        }
     if (!h->sorted_ok) {   // first positions (or a box change pending): lay the tiles out from these coordinates
         HIP_OK(h, hipStreamSynchronize(h->stream));
         h->hx = st;
@@ -3921,7 +4003,7 @@ int blues_get_stats(BluesEngine* h, int64_t stats[BLUES_N_STATS]) {
         std::vector<int> ic, oc; hipSetDevice(h->device); hipStreamSynchronize(h->stream);
         try { h->d_ocount.download(oc); h->d_icount.download(ic); for (int c : oc) { stats[14] += c; stats[15] += (c + 63) / 64; } for (int c : ic) { stats[17] += c; stats[18] += (c + 63) / 64; } } catch (std::string&) {}
     }
-    stats[0] = h->st_passes; stats[2] = h->st_launches; stats[3] = h->n_itiles; stats[4] = (int64_t)h->clusters.size(); stats[5] = h->jcap; stats[6] = h->npart; stats[7] = h->seg_len * 1000 + h->wpb;
+    stats[0] = h->st_passes; stats[2] = h->st_launches; stats[3] = h->n_itiles; stats[4] = (int64_t)h->clusters.size() + h->n_gen(); stats[5] = h->jcap; stats[6] = h->npart; stats[7] = h->seg_len * 1000 + h->wpb;
     if (h->d_flags.p) { DevFlags f; hipSetDevice(h->device); hipStreamSynchronize(h->stream); if (hipMemcpy(&f, h->d_flags.p, sizeof f, hipMemcpyDeviceToHost) == hipSuccess) { stats[1] = f.list_gen; stats[10] = f.builds; stats[16] = f.prunes; } }
     stats[19] = (h->prune_on && h->k1_mode == 2) || (h->k1_mode == 3 && h->frag_m < h->skin);
     stats[21] = h->int_threads;
@@ -4192,6 +4274,25 @@ static int stage_edit_list(BluesEngine* h, const int32_t* idx, int n_idx, const 
 // array): the unchanged coordinates are restored device to device, the edited ones travel.  Returns 3 (and does nothing)
 // when an edited atom shares a constraint cluster with an atom that is not edited -- the cluster would have to be made
 // whole with coordinates only the device has; the caller then takes the plain host route.
+// the general clusters' part of the rule above: 3 if an edited atom shares a general cluster with one that is not edited, else every
+// edited general cluster is made one periodic image (pos_of: place in the edit list or -1; ed: its coordinates)
+static int gen_edit_whole(const BluesEngine* h, const std::vector<int>& pos_of, double* ed) {
+    size_t t = 0;
+    for (const GenCluster& G : h->gen_h) {
+        int inside = 0;
+        for (int a = 0; a < G.na; a++) inside += pos_of[h->gen_atoms_h[G.a0 + a].atom] >= 0;
+        const size_t t1 = t + 2 * (size_t)(G.na - 1);
+        if (inside != 0 && inside != G.na) return 3;
+        if (inside) for (size_t q = t; q < t1; q += 2)
+            for (int k = 0; k < 3; k++) {
+                const double d = ed[3 * pos_of[h->gen_tree[q]] + k] - ed[3 * pos_of[h->gen_tree[q + 1]] + k];
+                ed[3 * pos_of[h->gen_tree[q]] + k] -= lattice_shift(h, k, d);
+            }
+        t = t1;
+    }
+    return 0;
+}
+
 int blues_set_positions_from_snapshot_edited(BluesEngine* h, const BluesSnapshot* sn, const int32_t* idx, int32_t n_idx, const double* xyz) {
     if (snapshot_usable(h, sn)) return 1;
     if (!sn->has_x) E_FAIL(h, "the snapshot holds no positions");
@@ -4211,6 +4312,7 @@ int blues_set_positions_from_snapshot_edited(BluesEngine* h, const BluesSnapshot
                 ed[3 * pos_of[c.atoms[a]] + k] -= lattice_shift(h, k, d);
             }
     }
+    if (gen_edit_whole(h, pos_of, ed.data())) return 3;
     HIP_OK(h, hipSetDevice(h->device));
     if (before_position_edit(h)) return 1;
     if (sn->owner->stream != h->stream) HIP_OK(h, hipStreamSynchronize(sn->owner->stream));
@@ -4464,6 +4566,7 @@ static int batch_restore_impl(BluesBatch* B, BluesSnapshot* const* snaps, int wh
                             e0[3 * pos_of[c.atoms[a]] + k] -= lattice_shift(h, k, d);
                         }
                 }
+                if (gen_edit_whole(h, pos_of, e0)) return 3;
             }
         }
     }
@@ -4722,3 +4825,8 @@ int blues_batch_time_nonbonded(BluesBatch* b, int32_t reps, double* usec) {
 }
 
 }  // extern "C"
+
+#ifdef BLUES_GEN_SWEEPS
+// measuring builds only (-DBLUES_GEN_SWEEPS; profiles/general_constraints): SHAKE calls of the general solver, their sweeps in all, most sweeps of one call
+extern "C" int blues_debug_gen_sweeps(unsigned long long out[3]) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gen_sweeps), 3 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1; }
+#endif

@@ -294,6 +294,14 @@ __global__ void __launch_bounds__(256) k_integrate_b(const RepCore* __restrict__
     integrate_body(A, d.prog);
 }
 
+// a chain with general constraint clusters (kernels_constraints.h): the same dispatch as the lone engine's k_integrate_gen, on the
+// (block, member) grid of k_integrate_b -- the interpreter reads each atom once, so there is no L2 reuse for the XCD map to keep
+__global__ void __launch_bounds__(256) k_integrate_gen_b(const RepCore* __restrict__ reps, IntDyn d) {
+    if (!reps[blockIdx.y].active) return;
+    IntArgs A = reps[blockIdx.y].in; apply_dyn(A, d, reps[blockIdx.y].draw_delta);
+    integrate_gen_dispatch(A, d.prog);
+}
+
 // the measuring interpreter of the energy ledger (kernels_integrate.h: integrate_body<true>) and its two device-side sums, one
 // workgroup per member: the same bodies as the lone engine's kernels
 __global__ void __launch_bounds__(256) k_integrate_led_b(const RepCore* __restrict__ reps, IntDyn d) {

@@ -60,9 +60,12 @@ struct ClusterRec {
     double w[4];     // 1/mass (0 for empty slots)
 };
 
+struct GenCluster; struct GenAtom; struct GenCons;   // general constraint clusters: kernels_constraints.h
 struct IntArgs {
     int n, n_clusters;
     const ClusterRec* recs;
+    // general clusters (null / 0: none): their records, and the first of their workgroups at the tail of the interpreter's grid
+    const GenCluster* gen; const GenAtom* gen_atoms; const GenCons* gen_cons; int n_gen, gen_block0;
     double* x[3]; double* v[3];
     const double* mass;
     // force sources
@@ -755,6 +758,7 @@ _Pragma("unroll") for (int a = 0; a < 4; a++) if (a < C.na) for (int k = 0; k < 
 
 __global__ void __launch_bounds__(256) k_integrate(IntArgs A) { integrate_body(A, A.prog); }
 __global__ void __launch_bounds__(256) k_integrate_led(IntArgs A) { integrate_body<true>(A, A.prog); }
+#include "kernels_constraints.h"
 
 // ---- energy ledger: the device-side sums.  One workgroup of 64 threads per chain; no atomics, every sum in a fixed order.
 // k_ledger_ke: the blocks' KE partials of the launch before, in block order, into heat and shadow_work.
