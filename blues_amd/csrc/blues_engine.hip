@@ -312,6 +312,7 @@ struct BluesEngine {
     DBuf<unsigned short> d_alist, d_plist; DBuf<int> d_acount, d_pcount, d_pneed; DBuf<unsigned> d_xprune[3];   // pruned lists (by i-slot)
     DBuf<uint4> d_pimg4; DBuf<float2> d_pimg2; DBuf<int> d_mlist, d_mcount; int mcap = 0;   // packed group images (ListArgs)
     DBuf<unsigned short> d_aself; DBuf<uint4> d_pimgb; DBuf<int> d_sx_row;
+    float alist_pf_reach = 0.8f;   // ListArgs.pf_reach (nm): the reach up to which a wave of the atoms'-list builder prefilters its group's list; < 0: never.  Development switch: blues_set_global "atom_list_prefilter"
     int n_entries = 0;
     int int_blocks = 1, int_threads = 128;
     bool clusters_packed = false;   // BluesTuning.pack_clusters took effect (build_clusters): a 128-thread block may run the fused step kernel
@@ -1496,7 +1497,7 @@ static ListArgs make_list_args(BluesEngine* h) {
     if (h->k1_mode == 2) { a.alist = h->d_alist.p; a.acount = h->d_acount.p; a.acap = h->acap; }
     a.S = h->S; a.n_lists = h->n_lists; a.hint_count = h->hint_count; a.no_sphere = h->tune.no_sphere;
     if (h->k1_mode == 2 && h->prune_on) { a.pneed = h->d_pneed.p; a.plist = h->d_plist.p; a.pcount = h->d_pcount.p; for (int k = 0; k < 3; k++) a.xprune[k] = h->d_xprune[k].p; }
-    if (h->k1_mode == 2) { a.pimg4 = h->d_pimg4.p; a.pimg2 = h->d_pimg2.p; a.mlist = h->d_mlist.p; a.mcount = h->d_mcount.p; a.mcap = h->mcap; a.aself = h->d_aself.p; a.pimgb = h->d_pimgb.p; a.sx_row = h->d_sx_row.p; }
+    if (h->k1_mode == 2) { a.pimg4 = h->d_pimg4.p; a.pimg2 = h->d_pimg2.p; a.mlist = h->d_mlist.p; a.mcount = h->d_mcount.p; a.mcap = h->mcap; a.aself = h->d_aself.p; a.pimgb = h->d_pimgb.p; a.sx_row = h->d_sx_row.p; a.pf_reach = h->alist_pf_reach; }
     return a;
 }
 
@@ -3949,6 +3950,10 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
 int blues_set_global(BluesEngine* h, const char* name, double value) {
     HIP_OK(h, hipSetDevice(h->device));
     std::string k(name);
+    // development switch of the atoms'-list builder (kernels_nb.h: build_atom_lists_body), not an integrator variable: 0: every wave
+    // takes the direct walk; N > 0: waves whose atoms lie within N picometres of their centre prefilter their group's list (default
+    // 800: scripts/census_atom_list_prefilter.py).  The lists are the same either way; the Python loader maps BLUES_ATOM_LIST_PREFILTER onto it
+    if (k == "atom_list_prefilter") { h->alist_pf_reach = value <= 0.0 ? -1.0f : (float)(std::min(value, 1e5) * 1e-3); return 0; }
     if (k == "protocol_work" || (k == "shadow_work" && (h->led_flags & LED_SHADOW)) || (k == "heat" && (h->led_flags & LED_HEAT))) {
         DevAccum a; if (read_acc(h, &a)) return 1;
         if (k == "protocol_work") a.protocol_work = value; else if (k == "heat") a.heat = value; else a.shadow_work = value;

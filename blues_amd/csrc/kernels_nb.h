@@ -69,6 +69,7 @@ struct ListArgs {
     unsigned short* aself;   // [n_islots] every i-atom's own entry in its group's list (NB_ENT form; 0xffff: not there), written with the atoms' lists
     uint4* pimgb;            // [n_lists][jcap] what the builder of the atoms' lists streams: {x, y, z, sorted atom index | mobile << 31}
     const int* sx_row;       // [n_islots][SX_ROW] static per i-slot: the atom's sorted index, its excluded partners, count / min / max (build_atom_lists_body)
+    float pf_reach;          // prefilter of build_atom_lists_body: a wave whose atoms lie within this of their centre (nm) walks the prefiltered list; < 0: no wave does
 };
 
 // LIST_WAVES waves share one tile's scan of all n atoms; each wave keeps LIST_PREFETCH independent loads in flight.
@@ -84,7 +85,8 @@ struct ListArgs {
 #define ATOM_LIST_THREADS (ATOM_LIST_WAVES * 64)   // lane fits exactly where a workgroup of the alchemical kernel retires
 #define ATOM_LIST_U 2                       // atoms per wave (one atom per wave and twice the workgroups: 60 us against 57 at R = 512)
 #define ATOM_LIST_PARTS (64 / (ATOM_LIST_WAVES * ATOM_LIST_U))    // its blocks per i-tile
-#define ATOM_SLOT(part, wv, u) ((part) * (64 / ATOM_LIST_PARTS) + (wv) + ATOM_LIST_WAVES * (u))
+#define ATOM_SLOT(part, wv, u) ((part) * (64 / ATOM_LIST_PARTS) + (wv) * ATOM_LIST_U + (u))   // a wave's slots are ADJACENT: neighbours in the sort order, one small sphere for its prefilter (build_atom_lists_body)
+#define ATOM_LIST_RING 128                  // records of a wave's LDS ring between the prefilter and the walk: fewer than 64 wait when a chunk's (at most 64) survivors arrive
 #define LIST_LDS 8192      // j-list entries mirrored in LDS for the exclusion searches (longer lists are searched in HBM)
 // per-atom-list mode (nonbonded_atom_body): layout of the dynamic LDS and of a list entry
 #define NB_LQ_BYTES 51200   // room for 6400 {sigma/2, 2 sqrt(eps)} records at the bottom of the dynamic LDS; the {x,y,z,q} records follow
@@ -367,6 +369,23 @@ __global__ void __launch_bounds__(LIST_THREADS) k_build_lists(ListArgs a, NbCons
 // A difference of fixed-point coordinates IS the minimum image (the box spans 2^32), so there is no reference point and no wrap.
 // The running counts live in vector registers (v_bcnt / v_mbcnt) -- a CU has ONE scalar ALU for its 16 waves.
 // The pair kernel tests r < cutoff itself; what must hold here is "within cutoff+skin now" (float, with margin).
+// PREFILTER.  An atom keeps ~700 of the ~4,000 candidates of its group's list, and the tests above cost ~90 instructions per chunk
+// and atom.  A wave's atoms are neighbours in the sort order (ATOM_SLOT), so the wave first tests every chunk ONCE against the
+// sphere that holds its atoms -- centre c, reach = the largest minimum-image distance of one of them from c -- and compacts the
+// survivors, in list order, {record, list position k}, into a ring of ATOM_LIST_RING records in LDS; whenever 64 wait there the
+// unchanged walk takes them as its next chunk, and what is left when the list ends as its last.  The walk sees a shorter
+// list in the SAME order with every record's own k, so exclusion ranges (jfirst / jlast: still ascending), the atom's own
+// place and every output are what the direct walk gives: same entries, same order, same counts.
+// Why nothing is lost: minimum-image distance is a metric on the torus, so for a candidate j and an atom u of the wave
+// |x_j - x_u| >= |x_j - c| - |x_u - c| >= |x_j - c| - reach.  The prefilter drops j only if |x_j - c|^2 >= (R_j + reach)^2 * 1.0002
+// with R_j^2 the walk's OWN limit for that candidate (rl2 / rl2m, margin included) and reach rounded up by 1.0001: j is then
+// outside R_j of every atom of the wave by 1e-4 of the distance, a thousand times the rounding of the float arithmetic
+// (~1e-7 per operation, a dozen operations), and fails the walk's strict test d2 < lim.
+// A ring needs no room for a worst case, so no wave can overflow it, and there is no barrier: a wave writes and reads its own ring.
+// A wave takes the direct walk from global memory (both paths: one loop) where its reach exceeds ListArgs.pf_reach: census
+// (scripts/census_atom_list_prefilter.py) -- the filter costs ~1/6 of a direct walk, so it pays while less than ~0.85 of the list
+// survives, and units of the flagship with a reach of 0.8 nm keep that much; its pairs of slots have a reach of 0.14 nm (mean;
+// 0.61 at most) and keep 0.25 (0.55).  A wave with no atom (the last tile's empty slots) walks nothing.
 #define ATOM_LIST_PF 8      // chunks of 64 candidates in flight per wave (a load from the image the previous kernel wrote takes ~2,000 cycles, a chunk's tests ~300)
 #define SX_ROW 32           // ints per i-slot in sx_row: [0] the atom's sorted index (-1: empty slot), [1 .. n-1] its excluded partners, [28] n, [29] min, [30] max of the row
 #define SX_MAX 28
@@ -414,6 +433,36 @@ __device__ __forceinline__ void build_atom_lists_body(const ListArgs& a, const N
     const bool dual = a.plist != nullptr;
     float rp2 = c.rp2 * 1.0001f + 1e-5f, rp2m = c.rp2_m * 1.0001f + 1e-5f;   // (same safety margin as the full lists)
     asm volatile("" : "+v"(cfx), "+v"(cfy), "+v"(cfz), "+v"(rl2), "+v"(rl2m), "+v"(rp2), "+v"(rp2m));   // (vector-register operands: kernels_nb.h, "Round 4")
+    // ---- prefilter: the sphere of the wave's atoms (fixed-point differences: minimum image, as in the walk; empty slots skipped)
+    __shared__ uint4 s_ring[ATOM_LIST_WAVES][ATOM_LIST_RING];
+    __shared__ unsigned short s_ringk[ATOM_LIST_WAVES][ATOM_LIST_RING];
+    uint4* const ring = s_ring[wv]; unsigned short* const ringk = s_ringk[wv];
+    int nocc = 0, ufirst = 0;
+#pragma unroll
+    for (int u = ATOM_LIST_U - 1; u >= 0; u--) if (ia4[u] >= 0) { nocc++; ufirst = u; }
+    uint32_t cx[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        uint32_t xf = xi4[0][k];
+#pragma unroll
+        for (int u = 1; u < ATOM_LIST_U; u++) if (ufirst == u) xf = xi4[u][k];
+        int32_t off = 0;   // (each offset divided before the sum: no overflow; any centre is a valid one, the reach is measured from it)
+#pragma unroll
+        for (int u = 0; u < ATOM_LIST_U; u++) if (ia4[u] >= 0) off += (int32_t)(xi4[u][k] - xf) / max(nocc, 1);
+        cx[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(xf + (uint32_t)off));   // (the same in every lane: a scalar operand)
+    }
+    float reach2 = 0.0f;
+#pragma unroll
+    for (int u = 0; u < ATOM_LIST_U; u++) {
+        const float dx = (float)(int32_t)(xi4[u][0] - cx[0]) * cfx, dy = (float)(int32_t)(xi4[u][1] - cx[1]) * cfy, dz = (float)(int32_t)(xi4[u][2] - cx[2]) * cfz;
+        if (ia4[u] >= 0) reach2 = fmaxf(reach2, fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
+    }
+    const float reach = sqrtf(reach2) * 1.0001f + 1e-6f;
+    float fl2 = (sqrtf(rl2) + reach) * (sqrtf(rl2) + reach) * 1.0002f, fl2m = (sqrtf(rl2m) + reach) * (sqrtf(rl2m) + reach) * 1.0002f;
+    asm volatile("" : "+v"(fl2), "+v"(fl2m));
+    const bool direct = !(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, reach))) <= a.pf_reach);   // wave-uniform
+    const int nwalk = nocc ? nch : 0;   // (a wave without an atom: empty lists, written below)
+    int head = 0, tail = 0;             // the ring holds records [head, tail) modulo its size; wave-uniform
     int cntv[ATOM_LIST_U], cntp[ATOM_LIST_U];
     unsigned short* out4[ATOM_LIST_U]; unsigned short* outp4[ATOM_LIST_U];
 #pragma unroll
@@ -424,57 +473,81 @@ __device__ __forceinline__ void build_atom_lists_body(const ListArgs& a, const N
     const float INF = __builtin_inff();
     const int acap1 = a.acap - 1;
     NB_STAMP(t == 0 && tid == 0, 7);
-    for (int ch0 = 0; ch0 < nch; ch0 += ATOM_LIST_PF) {
+    // one chunk of the walk: 64 candidates `cur` at list positions k, in list order; !valid: a lane past the end (it holds the last record again)
+    auto walk = [&](const uint4 cur, const int k, const bool valid) __attribute__((always_inline)) {
+        const bool mob = (int)cur.w < 0;
+        const int js = (int)(cur.w & 0x7fffffffu);
+        const unsigned short ent = NB_ENT(k);   // (the LDS index times 8: nonbonded_atom_body; "mobile" travels as the sign of the image's sigma/2)
+        const float kinf = valid ? 0.0f : INF;
+        const float lim = mob ? rl2m : rl2, plim = mob ? rp2m : rp2;
+        const int jfirst = __builtin_amdgcn_readfirstlane(js), jlast = __builtin_amdgcn_readlane(js, 63);   // (the list is ascending)
+#pragma unroll
+        for (int u = 0; u < ATOM_LIST_U; u++) {
+            bool excluded = false;
+            if (jlast >= rmin4[u] && jfirst <= rmax4[u]) {   // wave-uniform; a handful of chunks per atom
+                for (int e = 0; e < nrow4[u]; e++) excluded |= js == __builtin_amdgcn_readlane(rowv[u], e);
+                if (js == ia4[u] && valid) a.aself[t * 64 + ATOM_SLOT(part, wv, u)] = ent;   // (the atom itself: its own place in the list)
+            }
+            const float dx = (float)(int32_t)(cur.x - xi4[u][0]) * cfx, dy = (float)(int32_t)(cur.y - xi4[u][1]) * cfy, dz = (float)(int32_t)(cur.z - xi4[u][2]) * cfz;
+            float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) + kinf;
+            d2 = excluded ? INF : d2;
+            const bool pass = d2 < lim && ia4[u] >= 0;   // (an empty slot passes nobody)
+            const unsigned long long bal = __ballot(pass);
+            const unsigned blo = (unsigned)bal, bhi = (unsigned)(bal >> 32);
+            const int pos = cntv[u] + (int)__builtin_amdgcn_mbcnt_hi(bhi, __builtin_amdgcn_mbcnt_lo(blo, 0u));
+            // running count on the vector ALU.  gfx950 needs two wait states between a VALU write of an SGPR / VCC (the
+            // compare behind the ballot) and a VALU read of it as an operand; the compiler inserts them for its own
+            // instructions but not around inline assembly (without the s_nop the counts came out stale)
+            int c2;
+            asm("s_nop 1\n\tv_bcnt_u32_b32 %0, %1, %3\n\tv_bcnt_u32_b32 %0, %2, %0" : "=&v"(c2) : "s"(blo), "s"(bhi), "v"(cntv[u]));
+            cntv[u] = c2;
+            if (pass) out4[u][min(pos, acap1)] = ent;   // on overflow (flagged below) the surplus lands on the last entry
+            if (dual) {   // (block-uniform) the pruned list: the same entries within cutoff + inner margin, same order
+#if defined(NB_PRUNE_MOBILE_BY_BUILD_POSITION)
+                const bool keep = pass && d2 < plim;
+#else
+                const bool keep = pass && (mob || d2 < plim);   // (mobile candidates of the full list always stay: nonbonded_atom_body)
+#endif
+                const unsigned long long bk = __ballot(keep);
+                const unsigned klo = (unsigned)bk, khi = (unsigned)(bk >> 32);
+                const int ppos = cntp[u] + (int)__builtin_amdgcn_mbcnt_hi(khi, __builtin_amdgcn_mbcnt_lo(klo, 0u));
+                int c3;
+                asm("s_nop 1\n\tv_bcnt_u32_b32 %0, %1, %3\n\tv_bcnt_u32_b32 %0, %2, %0" : "=&v"(c3) : "s"(klo), "s"(khi), "v"(cntp[u]));
+                cntp[u] = c3;
+                if (keep) outp4[u][min(ppos, acap1)] = ent;
+            }
+        }
+    };
+    for (int ch0 = 0; ch0 < nwalk; ch0 += ATOM_LIST_PF) {
 #pragma unroll
         for (int d = 0; d < ATOM_LIST_PF; d++) {
             const int ch = ch0 + d;
-            if (ch >= nch) break;   // wave-uniform
-            const uint4 cur = pf[d];
-            if (ch + ATOM_LIST_PF < nch) pf[d] = fetch(ch + ATOM_LIST_PF);   // (in flight while the next chunks are tested)
-            const int k = ch * 64 + lane;
-            const bool mob = (int)cur.w < 0;
-            const int js = (int)(cur.w & 0x7fffffffu);
-            const unsigned short ent = NB_ENT(k);   // (the LDS index times 8: nonbonded_atom_body; "mobile" travels as the sign of the image's sigma/2)
-            const float kinf = k < count ? 0.0f : INF;
-            const float lim = mob ? rl2m : rl2, plim = mob ? rp2m : rp2;
-            const int jfirst = __builtin_amdgcn_readfirstlane(js), jlast = __builtin_amdgcn_readlane(js, 63);   // (the list is ascending)
-#pragma unroll
-            for (int u = 0; u < ATOM_LIST_U; u++) {
-                bool excluded = false;
-                if (jlast >= rmin4[u] && jfirst <= rmax4[u]) {   // wave-uniform; a handful of chunks per atom
-                    for (int e = 0; e < nrow4[u]; e++) excluded |= js == __builtin_amdgcn_readlane(rowv[u], e);
-                    if (js == ia4[u] && k < count) a.aself[t * 64 + ATOM_SLOT(part, wv, u)] = ent;   // (the atom itself: its own place in the list)
-                }
-                const float dx = (float)(int32_t)(cur.x - xi4[u][0]) * cfx, dy = (float)(int32_t)(cur.y - xi4[u][1]) * cfy, dz = (float)(int32_t)(cur.z - xi4[u][2]) * cfz;
-                float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) + kinf;
-                d2 = excluded ? INF : d2;
-                const bool pass = d2 < lim && ia4[u] >= 0;   // (an empty slot passes nobody)
-                const unsigned long long bal = __ballot(pass);
-                const unsigned blo = (unsigned)bal, bhi = (unsigned)(bal >> 32);
-                const int pos = cntv[u] + (int)__builtin_amdgcn_mbcnt_hi(bhi, __builtin_amdgcn_mbcnt_lo(blo, 0u));
-                // running count on the vector ALU.  gfx950 needs two wait states between a VALU write of an SGPR / VCC (the
-                // compare behind the ballot) and a VALU read of it as an operand; the compiler inserts them for its own
-                // instructions but not around inline assembly (without the s_nop the counts came out stale)
-                int c2;
-                asm("s_nop 1\n\tv_bcnt_u32_b32 %0, %1, %3\n\tv_bcnt_u32_b32 %0, %2, %0" : "=&v"(c2) : "s"(blo), "s"(bhi), "v"(cntv[u]));
-                cntv[u] = c2;
-                if (pass) out4[u][min(pos, acap1)] = ent;   // on overflow (flagged below) the surplus lands on the last entry
-                if (dual) {   // (block-uniform) the pruned list: the same entries within cutoff + inner margin, same order
-#if defined(NB_PRUNE_MOBILE_BY_BUILD_POSITION)
-                    const bool keep = pass && d2 < plim;
-#else
-                    const bool keep = pass && (mob || d2 < plim);   // (mobile candidates of the full list always stay: nonbonded_atom_body)
-#endif
-                    const unsigned long long bk = __ballot(keep);
-                    const unsigned klo = (unsigned)bk, khi = (unsigned)(bk >> 32);
-                    const int ppos = cntp[u] + (int)__builtin_amdgcn_mbcnt_hi(khi, __builtin_amdgcn_mbcnt_lo(klo, 0u));
-                    int c3;
-                    asm("s_nop 1\n\tv_bcnt_u32_b32 %0, %1, %3\n\tv_bcnt_u32_b32 %0, %2, %0" : "=&v"(c3) : "s"(klo), "s"(khi), "v"(cntp[u]));
-                    cntp[u] = c3;
-                    if (keep) outp4[u][min(ppos, acap1)] = ent;
+            if (ch >= nwalk) break;   // wave-uniform
+            uint4 cur = pf[d];
+            if (ch + ATOM_LIST_PF < nwalk) pf[d] = fetch(ch + ATOM_LIST_PF);   // (in flight while the next chunks are tested)
+            int k = ch * 64 + lane;
+            bool go = true;
+            if (!direct) {   // wave-uniform.  The chunk's survivors join the ring; the walk takes a chunk from it once 64 wait
+                const float dx = (float)(int32_t)(cur.x - cx[0]) * cfx, dy = (float)(int32_t)(cur.y - cx[1]) * cfy, dz = (float)(int32_t)(cur.z - cx[2]) * cfz;
+                const bool keepc = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) < ((int)cur.w < 0 ? fl2m : fl2) && k < count;
+                const unsigned long long nb = __ballot(keepc);
+                const int w = (tail + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(nb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)nb, 0u))) & (ATOM_LIST_RING - 1);
+                if (keepc) { ring[w] = cur; ringk[w] = (unsigned short)k; }
+                tail += __popcll(nb);
+                go = tail - head >= 64;
+                if (go) {
+                    __builtin_amdgcn_wave_barrier();   // (the wave's own stores, its own loads: LDS serves a wave in order)
+                    const int r = (head + lane) & (ATOM_LIST_RING - 1);
+                    cur = ring[r]; k = ringk[r]; head += 64;
                 }
             }
+            if (go) walk(cur, k, direct ? k < count : true);
         }
+    }
+    if (!direct && tail > head) {   // what is left in the ring: the last chunk
+        __builtin_amdgcn_wave_barrier();
+        const int m = tail - head, r = (head + min(lane, m - 1)) & (ATOM_LIST_RING - 1);
+        walk(ring[r], ringk[r], lane < m);
     }
     NB_STAMP(t == 0 && tid == 0, 8);
 #pragma unroll

@@ -1,5 +1,6 @@
 """Thin ctypes wrapper over the C-ABI of include/blues_engine.h (one handle per replica)."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -36,6 +37,10 @@ class NativeEngine:
         self.n = system.n_atoms
         self.system = system
         self.integrator = integrator
+        # development switch of the atoms'-list builder: read here, when an engine is created -- the native library reads no environment
+        spec = os.environ.get("BLUES_ATOM_LIST_PREFILTER")
+        if spec:
+            self._check(self._lib.blues_set_global(self._h, b"atom_list_prefilter", float(int(spec))))
         if system.positions is not None:
             self.set_positions(system.positions)
 
