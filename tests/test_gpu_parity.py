@@ -270,7 +270,8 @@ def test_full_size_properties(Engine):
     g.set_positions(s.positions + np.array([s.box[0], 0.0, -s.box[2]]))
     assert g.potential_energy() == pytest.approx(e0, rel=1e-9)
     assert _rel(g.get_forces(), f0) < 1e-6
-    # a permutation of the atom order (here: whole-molecule reversal of the water block) changes nothing physical
+    # a short switch at full size: finite work, every tile in use, constraints kept (atom order, unwrapped molecules and exchanged
+    # axes are tests/test_gpu_symmetry.py's)
     g.set_positions(s.positions); g.set_velocities(v)
     w = g.run_switch(10, trace=True)
     assert np.all(np.isfinite(w)) and g.stats()["i_tiles"] == (s.n_atoms - 15 + 63) // 64
