@@ -431,8 +431,19 @@ static BluesBatch::EvPair* k1t_begin(BluesBatch* B, hipStream_t st) {
     return nullptr;
 }
 static void k1t_end(BluesBatch::EvPair* p, hipStream_t st) { if (p && hipEventRecord(p->b, st) == hipSuccess) p->busy = true; }
+// ---- forward declarations (the one block of them: layout, energies and the state hand-over call each other across the file)
 static int batch_enter(BluesBatch* B);
 static void batch_leave(BluesBatch* B);
+static int batch_plan_shape(BluesBatch* B, bool fresh);
+static int sort_and_tile(BluesEngine* h);
+static int relayout(BluesEngine* h);
+static BluesEngine* relayout_many(const std::vector<BluesEngine*>& members, const std::function<bool(BluesEngine*)>& prepare);
+static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
+static int load_positions(BluesEngine* h, const double* const src[3], int stride, int n_edit);
+static int total_energy(BluesEngine* h, double* E);
+static int kinetic_energy_now(BluesEngine* h, double* ke);
+static int switching_open(BluesEngine* h);
+static int switching_close(BluesEngine* h);
 static inline bool batch_dry(const BluesEngine* h) { return h->batch && h->batch->lockstep && h->batch->leader != h; }
 static inline bool batch_lead(const BluesEngine* h) { return h->batch && h->batch->lockstep && h->batch->leader == h; }
 static inline int* batch_req_ptr(const BluesEngine* h) { return h->batch && h->batch->sync_lists ? h->batch->d_req.p : nullptr; }
@@ -865,7 +876,6 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
 }
 
 // ------------------------------------------------------------------ spatial sort + tile image (host, at set_positions)
-static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
 // NoCutoff (k1_mode 4): the one layout of the engine's life, made at creation from the topology alone -- no spatial sort (the
 // "sorted" order is the caller's), no tiles to re-sort, no lists.  The i-slots are the mobile non-alchemical atoms in caller order;
 // the alchemical kernel's j-list is every environment atom, static; the partial slabs are shaped for k_finalize as the other modes
@@ -2077,10 +2087,6 @@ static int launch_pme(BluesEngine* h, int want_energy) {
     return h->precision == 0 ? launch_pme_t<float>(h, want_energy) : launch_pme_t<double>(h, want_energy);
 }
 
-static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
-static int sort_and_tile(BluesEngine* h);
-static int batch_plan_shape(BluesBatch* B, bool fresh);
-static BluesEngine* relayout_many(const std::vector<BluesEngine*>& members, const std::function<bool(BluesEngine*)>& prepare);
 static int resolve_xfer(BluesEngine* h) {
     if (!h->xfer_pending) return 0;
     h->xfer_pending = false;
@@ -2113,7 +2119,6 @@ static int resolve_xfer(BluesEngine* h) {
 // (its record is inactive) and is stepped by launches of its own behind them -- ~60 us per step for that one chain, nothing for the others --
 // until its atoms fit the batch's shape again (tried at the start of its next switch: a State that arrives from the MD leg or the restore
 // after a rejection brings the compact arrangement back).  Only when more than a handful of members straggle does the batch re-plan.
-static int relayout(BluesEngine* h);
 static bool batch_can_straggle(const BluesBatch* B, const BluesEngine* h) {
     if (h->straggler || h->k1_mode != 2 && h->shape_S == 0) return false;
     int n = 0; for (const BluesEngine* m : B->eng) n += m->straggler;
@@ -2348,8 +2353,6 @@ static int check_flags(BluesEngine* h) {
 // kernel raises resort_hint when a list nears its capacity; stepping polls it every RESORT_POLL steps (one small
 // read-back) and re-sorts from the positions on the device.  Without this a long all-mobile run ends in list_overflow.
 #define RESORT_POLL 64
-static int relayout(BluesEngine* h);
-static int batch_plan_shape(BluesBatch* B, bool fresh);
 // Fragment lists: the builder raises resort_hint when a row has reached 90 % of its capacity (kernels_frag.h: finish) as well as when its
 // blocks have spread.  Before the re-layout that follows, the rows' lengths say whether the lists want more room than the density estimate
 // gave them (a solute-rich region, a denser phase): then the next layout gets a quarter more -- before an entry is ever dropped.
@@ -2585,12 +2588,6 @@ static int need_pass(BluesEngine* h, int lo, int hi) {  // need slots covering L
     return force_pass(h, lo);
 }
 
-static int total_energy(BluesEngine* h, double* E);
-static int kinetic_energy_now(BluesEngine* h, double* ke);
-static int switching_open(BluesEngine* h);
-static int switching_close(BluesEngine* h);
-static int load_positions(BluesEngine* h, const double* const src[3], int stride, int n_edit);
-
 static int run_fragment(BluesEngine* h, const std::string& frag) {
     if (h->remove_cm && !h->pass_valid && !frag.empty() && frag[0] == 'L') {
         if (need_pass(h, h->h_lambda_step, h->h_lambda_step)) return 1;  // forces do not depend on velocities: evaluate them first
@@ -2638,6 +2635,42 @@ static int run_fragment(BluesEngine* h, const std::string& frag) {
 }
 
 static int splitting_pass(BluesEngine* h) { return run_fragment(h, h->split); }
+
+// ---- state events: what the host's flags and caches owe to a change that comes from outside the stepping loop.  Every list exists
+// once, here; a call site that owes more (or less) says so at the call.  The many single `pass_valid = false` elsewhere state local facts.
+// work bookkeeping for instantaneous moves: remember U(x_old, lambda) before overwriting (integrators.py:205)
+static int before_position_edit(BluesEngine* h) {
+    if (flush_program(h)) return 1;
+    if (h->switch_mode == BLUES_SWITCH_NONE && h->have_positions && h->h_first_step >= 1 && h->h_step > 0 && h->h_step < h->nsteps && !h->unpert_valid) {
+        double E;
+        if (total_energy(h, &E)) return 1;
+        h->h_unperturbed = E; h->unpert_valid = true;
+    }
+    return 0;
+}
+// The engine's positions were replaced (setPositions in any form, a State restored): there are some now (have_positions); the next step
+// books the work of an instantaneous Move (x_edited, step_head); U(x) changed from outside, so the energy ledger's bracket restarts
+// (led_open, led_dirty); the last force pass, its sums still to be formed and the energies known belong to the old coordinates
+// (pass_valid, fin_pending, ecache); the next pass builds its lists whatever the displacement since the last build says (lists_forced).
+static void positions_replaced(BluesEngine* h) {
+    h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false;
+    h->ecache.clear(); h->lists_forced = true;
+}
+// The engine's velocities were written from outside a step program: the momentum partials of the last force pass (vel_clean) and the
+// kinetic energy read back last (ke_cache) describe the old ones.
+static void velocities_replaced(BluesEngine* h) { h->vel_clean = false; h->ke_cache_valid = false; }
+// integrator.reset(), host part: the mirrored control state goes back to "before the first step" (integrators.py:240-249); a Move made
+// before the reset is not charged after it (unpert_valid, x_edited); the pass evaluated at the old lambda_step is dropped with its
+// pending sums (pass_valid, fin_pending); the switching integrators' counters go too (switching.py:1023-1036; batches hold none of
+// those, for them these are zero already).  The accumulators on the device, and the flags that go with zeroing them, are the caller's.
+static void protocol_rewound(BluesEngine* h) {
+    h->h_step = 0; h->h_lambda = 0.0; h->h_first_step = 0; h->h_perturbed = 0.0; h->h_unperturbed = 0.0; h->h_prop = 1; h->h_lambda_step = 0;
+    h->unpert_valid = false; h->x_edited = false; h->pass_valid = false; h->fin_pending = false;
+    h->sw_shadow = 0.0; h->sw_Einit = 0.0; h->sw_Efinal = 0.0; h->sw_naccept = 0; h->sw_ntrials = 0; h->sw_accept = 0;
+}
+// An alchemical parameter (or the lambda_step they are tabulated by) was set from outside: U changes under the same coordinates, so
+// the last pass and its pending sums are void (pass_valid, fin_pending) and the energy ledger's bracket restarts (led_open, led_dirty).
+static void parameters_changed(BluesEngine* h) { h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }
 
 // ---- host-side energy bookkeeping of the switching integrators (reference blues/switching.py; dead code there, so this is the
 // plain synchronous form: one total energy and one kinetic energy per velocity-Verlet step)
@@ -2692,11 +2725,10 @@ static int switching_close(BluesEngine* h) {
     h->sw_accept = (exp(-((ke + E) - h->sw_bracket_E0) / h->kT) - u >= 0.0) ? 1 : 0;   // Lepton step(x): 1 for x >= 0
     if (!h->sw_accept) {
         BluesSnapshot* sn = h->sw_saved;
-        const double* src[3] = {sn->x[0], sn->x[1], sn->x[2]};
-        if (load_positions(h, src, 1, 0)) return 1;
+        if (load_positions(h, sn->x, 1, 0)) return 1;
         h->x_edited = false;   // (not a Move: no external-perturbation work)
         hipLaunchKernelGGL(k_negated_copy3, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->n, sn->v[0], sn->v[1], sn->v[2], h->d_v[0].p, h->d_v[1].p, h->d_v[2].p);
-        h->st_launches++; h->vel_clean = false; h->ke_cache_valid = false;
+        h->st_launches++; velocities_replaced(h);
         if (total_energy(h, &E)) return 1;   // the energy of the restored positions at the current parameters
     }
     h->sw_Epert = E;   // "Epert = energy" after the step (switching.py:1357; the second randomisation does not move atoms)
@@ -3447,8 +3479,6 @@ int blues_engine_create(const BluesSystemDesc* s, const BluesIntegratorDesc* it,
     return 0;
 }
 
-static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src);
-
 // re-derive the tile layout and launch decomposition from the positions currently on the device
 static int relayout(BluesEngine* h) {
     if (nocut(h)) return sort_and_tile(h);   // (nothing to lay out again: see nocut_layout)
@@ -3665,42 +3695,75 @@ static int download_xyz(BluesEngine* h, double* xyz, DBuf<double>* src) {   // d
     return 0;
 }
 
-// Shared tail of setPositions: the new coordinates are already on the device (src, SoA stride 1 or interleaved stride 3).
-static int load_positions(BluesEngine* h, const double* const src[3], int stride, int n_edit) {
+// ---- kernel records of the state hand-over, for a lone call and as one member's entry of a batched one
+// k_load_positions: the engine's positions from src (SoA stride 1, or interleaved stride 3) with image refresh and the re-sort statistics
+static LoadPosArgs make_load_args(BluesEngine* h, const double* const src[3], int stride) {
     LoadPosArgs a; memset(&a, 0, sizeof a);
     a.n = h->n; a.stride = stride;
     for (int k = 0; k < 3; k++) { a.src[k] = src[k]; a.x[k] = h->d_x[k].p; a.x_sort[k] = h->d_x_sort[k].p; }
     a.mass = h->d_mass.p; a.alch_local = h->d_alch_local.p; a.sorted_of_orig = h->d_sorted_of_orig.p;
     a.img_f = h->precision == 0 ? h->d_img_f.p : nullptr; a.img_d = h->precision == 0 ? nullptr : h->d_img_d.p;
     a.box = make_box(h); a.out = h->d_xfer_out.p;
+    return a;
+}
+// k_edit_positions behind that load: the atoms idx[n_edit] overwritten by xyz[n_edit][3] (both on the device)
+static EditPosArgs make_edit_args(BluesEngine* h, const LoadPosArgs& load, int n_edit, const int* idx, const double* xyz) {
+    EditPosArgs e; memset(&e, 0, sizeof e);
+    e.n_edit = n_edit; e.idx = idx; e.xyz = xyz;
+    for (int k = 0; k < 3; k++) { e.x[k] = h->d_x[k].p; e.x_sort[k] = h->d_x_sort[k].p; }
+    e.mass = load.mass; e.alch_local = load.alch_local; e.sorted_of_orig = load.sorted_of_orig; e.img_f = load.img_f; e.img_d = load.img_d; e.box = load.box; e.out = load.out;
+    return e;
+}
+// k_copy_arrays: x (what bit 0) and / or v (bit 1), SoA to SoA, from the engine into a snapshot (capture) or back
+static Copy6Args make_state_copy_args(BluesEngine* h, const BluesSnapshot* sn, int what, bool capture) {
+    Copy6Args c; memset(&c, 0, sizeof c);
+    c.n = h->n; c.src_stride = 1; c.dst_stride = 1;
+    if (what & 1) for (int k = 0; k < 3; k++) { c.src[c.count] = capture ? h->d_x[k].p : sn->x[k]; c.dst[c.count++] = capture ? sn->x[k] : h->d_x[k].p; }
+    if (what & 2) for (int k = 0; k < 3; k++) { c.src[c.count] = capture ? h->d_v[k].p : sn->v[k]; c.dst[c.count++] = capture ? sn->v[k] : h->d_v[k].p; }
+    return c;
+}
+
+// Shared tail of setPositions: the new coordinates are already on the device (src, SoA stride 1 or interleaved stride 3).
+static int load_positions(BluesEngine* h, const double* const src[3], int stride, int n_edit) {
+    const LoadPosArgs a = make_load_args(h, src, stride);
     // (a verdict still pending from an earlier load is kept: the kernels only OR / max / add into it)
     if (!h->xfer_pending) HIP_OK(h, hipMemsetAsync(h->d_xfer_out.p, 0, 4 * sizeof(unsigned), h->stream));
     else if (h->xfer_stream != h->stream) HIP_OK(h, hipStreamSynchronize(h->xfer_stream));
     hipLaunchKernelGGL(k_load_positions, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, a);
     h->st_launches++;
     if (n_edit > 0) {   // the edit list is already in d_edit_idx / d_edit_xyz
-        EditPosArgs e; memset(&e, 0, sizeof e);
-        e.n_edit = n_edit; e.idx = h->d_edit_idx.p; e.xyz = h->d_edit_xyz.p;
-        for (int k = 0; k < 3; k++) { e.x[k] = h->d_x[k].p; e.x_sort[k] = h->d_x_sort[k].p; }
-        e.mass = a.mass; e.alch_local = a.alch_local; e.sorted_of_orig = a.sorted_of_orig; e.img_f = a.img_f; e.img_d = a.img_d; e.box = a.box; e.out = a.out;
-        hipLaunchKernelGGL(k_edit_positions, dim3((n_edit + 63) / 64), dim3(64), 0, h->stream, e);
+        hipLaunchKernelGGL(k_edit_positions, dim3((n_edit + 63) / 64), dim3(64), 0, h->stream, make_edit_args(h, a, n_edit, h->d_edit_idx.p, h->d_edit_xyz.p));
         h->st_launches++;
     }
     if (!h->h_xfer && hipHostMalloc((void**)&h->h_xfer, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) E_FAIL(h, "hipHostMalloc failed");
     HIP_OK(h, hipMemcpyAsync(h->h_xfer, h->d_xfer_out.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     h->xfer_pending = true; h->xfer_stream = h->stream; h->xfer_src = h->h_xfer;
-    h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false; h->ecache.clear();
-    h->lists_forced = true;
+    positions_replaced(h);
     return 0;
 }
 
-// work bookkeeping for instantaneous moves: remember U(x_old, lambda) before overwriting (integrators.py:205)
-static int before_position_edit(BluesEngine* h) {
-    if (flush_program(h)) return 1;
-    if (h->switch_mode == BLUES_SWITCH_NONE && h->have_positions && h->h_first_step >= 1 && h->h_step > 0 && h->h_step < h->nsteps && !h->unpert_valid) {
-        double E;
-        if (total_energy(h, &E)) return 1;
-        h->h_unperturbed = E; h->unpert_valid = true;
+// Every constraint cluster as one whole periodic image, each atom brought beside the cluster's first (a lattice translation of single
+// atoms is physically a no-op); the cluster solves in k_integrate then need no minimum-image arithmetic.  xyz: [.][3]; pos_of: null
+// where xyz holds every atom in order, else an atom's place in an edit list or -1.  Returns 3, for the caller to do nothing, when an
+// edited atom shares a cluster with one that is not edited: the cluster would have to be made whole with coordinates only the device has.
+static int clusters_whole(const BluesEngine* h, double* xyz, const int* pos_of) {
+    auto at = [&](int atom) { return pos_of ? pos_of[atom] : atom; };
+    auto beside = [&](int a, int a0) { for (int k = 0; k < 3; k++) { const double d = xyz[3 * a + k] - xyz[3 * a0 + k]; xyz[3 * a + k] -= lattice_shift(h, k, d); } };
+    for (const HostCluster& c : h->clusters) {
+        int inside = 0, total = 0;
+        for (int a = 0; a < 4; a++) if (c.atoms[a] >= 0) { total++; inside += at(c.atoms[a]) >= 0; }
+        if (inside == 0) continue;
+        if (inside != total) return 3;
+        for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0) beside(at(c.atoms[a]), at(c.atoms[0]));
+    }
+    size_t t = 0;
+    for (const GenCluster& G : h->gen_h) {   // general clusters: every atom beside the one it is constrained to, from the first atom outwards
+        int inside = 0;
+        for (int a = 0; a < G.na; a++) inside += at(h->gen_atoms_h[G.a0 + a].atom) >= 0;
+        const size_t t1 = t + 2 * (size_t)(G.na - 1);
+        if (inside != 0 && inside != G.na) return 3;
+        if (inside) for (size_t q = t; q < t1; q += 2) beside(at(h->gen_tree[q]), at(h->gen_tree[q + 1]));
+        t = t1;
     }
     return 0;
 }
@@ -3709,25 +3772,15 @@ int blues_set_positions(BluesEngine* h, const double* xyz, int32_t n_atoms) {
     if (n_atoms != h->n) E_FAIL(h, "expected %d atoms, got %d", h->n, n_atoms);
     HIP_OK(h, hipSetDevice(h->device));
     if (before_position_edit(h)) return 1;
-    // store every constraint cluster as one whole periodic image (a lattice translation of single atoms is
-    // physically a no-op); the cluster solves in k_integrate then need no minimum-image arithmetic
     static thread_local std::vector<double> st;   // (staging of one host transfer: per thread, not per engine -- 560 KB x 2048 chains otherwise)
     st.assign(xyz, xyz + 3 * (size_t)h->n);
-    for (const HostCluster& c : h->clusters) for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0)
-        for (int k = 0; k < 3; k++) {
-            double d = st[3 * c.atoms[a] + k] - st[3 * c.atoms[0] + k];
-            st[3 * c.atoms[a] + k] -= lattice_shift(h, k, d);
-        }
-    for (size_t q = 0; q < h->gen_tree.size(); q += 2)   // general clusters: every atom beside the one it is constrained to, from the first atom outwards
-        for (int k = 0; k < 3; k++) {
-            const double d = st[3 * h->gen_tree[q] + k] - st[3 * h->gen_tree[q + 1] + k];
-            st[3 * h->gen_tree[q] + k] -= lattice_shift(h, k, d);
-        }
+    clusters_whole(h, st.data(), nullptr);
     if (!h->sorted_ok) {   // first positions (or a box change pending): lay the tiles out from these coordinates
         HIP_OK(h, hipStreamSynchronize(h->stream));
         h->hx = st;
         if (upload_xyz(h, h->hx.data(), h->d_x)) return 1;
-        h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false; h->ecache.clear(); h->e_frozen_valid = false; h->pme_static_valid = false;
+        positions_replaced(h);
+        h->e_frozen_valid = false; h->pme_static_valid = false;   // (no load kernel ran to say whether a frozen atom moved, resolve_xfer: the frozen-frozen constant and the static mesh part count as stale)
         return sort_and_tile(h);
     }
     // one interleaved transfer; de-interleaving, image refresh and the re-sort statistics happen on the device
@@ -3741,7 +3794,7 @@ int blues_set_velocities(BluesEngine* h, const double* xyz, int32_t n_atoms) {
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
     HIP_OK(h, hipStreamSynchronize(h->stream));
-    h->vel_clean = false; h->ke_cache_valid = false;
+    velocities_replaced(h);
     return upload_xyz(h, xyz, h->d_v);
 }
 
@@ -3822,7 +3875,7 @@ int blues_set_velocities_to_temperature(BluesEngine* h, double temperature, uint
     if (flush_program(h)) return 1;
     hipLaunchKernelGGL(k_maxwell, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, h->n, h->d_mass.p, h->d_v[0].p, h->d_v[1].p, h->d_v[2].p, KB_KJ * temperature, (unsigned long long)seed, (unsigned)h->replica * 4u + 1u);
     h->st_launches++;
-    h->vel_clean = false; h->ke_cache_valid = false;
+    velocities_replaced(h);
     if (emit(h, OP_RATTLE)) return 1;
     // (no read-back here: a velocity-constraint failure stays flagged on the device and is raised by the next step, which
     // checks the flags anyway -- a synchronous check per chain was 20 us of host time for each of R chains per iteration)
@@ -3962,7 +4015,7 @@ int blues_set_global(BluesEngine* h, const char* name, double value) {
     }
     else if (k == "step") h->h_step = (int)value;
     else if (k == "lambda") h->h_lambda = value;
-    else if (k == "lambda_step") { h->h_lambda_step = (int)value; h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }   // (energy ledger: U changes from outside, the bracket restarts)
+    else if (k == "lambda_step") { h->h_lambda_step = (int)value; parameters_changed(h); }
     else if (k == "first_step") h->h_first_step = (int)value;
     else if (k == "prop") h->h_prop = (int)value;
     else if (k == "nprop") h->nprop = (int)value;
@@ -3972,8 +4025,8 @@ int blues_set_global(BluesEngine* h, const char* name, double value) {
     else if (h->switch_mode != BLUES_SWITCH_NONE && (k == "total_work" || k == "naccept" || k == "ntrials")) {
         if (k == "naccept") h->sw_naccept = (int)value; else if (k == "ntrials") h->sw_ntrials = (int)value;   // (total_work is derived)
     }
-    else if (k == "lambda_sterics") { h->cur_ls = value; h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }
-    else if (k == "lambda_electrostatics") { h->cur_le = value; h->pass_valid = false; h->fin_pending = false; h->led_open = false; h->led_dirty = false; }
+    else if (k == "lambda_sterics") { h->cur_ls = value; parameters_changed(h); }
+    else if (k == "lambda_electrostatics") { h->cur_le = value; parameters_changed(h); }
     else E_FAIL(h, "global variable '%s' cannot be set", name);
     return 0;
 }
@@ -3981,12 +4034,10 @@ int blues_set_global(BluesEngine* h, const char* name, double value) {
 int blues_reset(BluesEngine* h) {
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
-    h->h_step = 0; h->h_lambda = 0.0; h->h_first_step = 0; h->h_perturbed = 0.0; h->h_unperturbed = 0.0; h->h_prop = 1; h->h_lambda_step = 0;
-    h->unpert_valid = false; h->x_edited = false; h->pass_valid = false; h->fin_pending = false;
+    protocol_rewound(h);
     if (h->led_flags) { hipLaunchKernelGGL(k_ledger_reset, dim3(1), dim3(1), 0, h->stream, h->d_acc.p, 1); h->st_launches++; h->led_open = false; h->led_dirty = false; }   // (shadow_work goes, heat stays: orc_reset)
     else HIP_OK(h, hipMemsetAsync(h->d_acc.p, 0, sizeof(DevAccum), h->stream));
     h->acc_cache_valid = false;
-    h->sw_shadow = 0.0; h->sw_Einit = 0.0; h->sw_Efinal = 0.0; h->sw_naccept = 0; h->sw_ntrials = 0; h->sw_accept = 0;   // switching.py:1023-1036
     return 0;
 }
 
@@ -4163,28 +4214,36 @@ int blues_batch_mesh_energy(BluesBatch* B, int32_t with_alchemical_charges, cons
 }
 
 // ---- State snapshots (include/blues_engine.h, "Device-resident State")
+// A snapshot of h to capture `what` (bit 0: positions, bit 1: velocities) into: from the engine's pool or newly allocated (null: no
+// memory), marked with what it will hold, the energies known for the positions and the box they are known in.  The copy is the caller's.
+static BluesSnapshot* snapshot_take(BluesEngine* h, int what) {
+    BluesSnapshot* sn = nullptr;
+    if (!h->snap_pool.empty()) { sn = h->snap_pool.back(); h->snap_pool.pop_back(); }
+    else {
+        sn = new BluesSnapshot(); sn->owner = h; sn->n = h->n;
+        if (hipMalloc((void**)&sn->block, sizeof(double) * 6 * (size_t)h->n) != hipSuccess) { delete sn; return nullptr; }
+        for (int k = 0; k < 3; k++) { sn->x[k] = sn->block + (size_t)k * h->n; sn->v[k] = sn->block + (size_t)(3 + k) * h->n; }
+    }
+    sn->has_x = what & 1; sn->has_v = (what & 2) != 0;
+    sn->ecache = h->ecache; if (!(what & 1)) sn->ecache.clear();
+    sn->box_epoch = h->box_epoch;
+    return sn;
+}
+// the launch that fills a snapshot, in its owner's books
+static void snapshot_copy_launched(BluesEngine* h) {
+    h->st_launches++;
+    if (h->acc_cache_valid && h->acc_cache_stamp + 1 == h->st_launches) h->acc_cache_stamp = h->st_launches;   // (a copy of x, v does not touch the accumulators)
+}
+
 int blues_snapshot_capture(BluesEngine* h, int32_t what, BluesSnapshot** out) {
     if (!out || !(what & 3)) E_FAIL(h, "snapshot: nothing requested");
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
     if ((what & 1) && !h->have_positions) E_FAIL(h, "positions have not been set");
-    BluesSnapshot* sn = nullptr;
-    if (!h->snap_pool.empty()) { sn = h->snap_pool.back(); h->snap_pool.pop_back(); }
-    else {
-        sn = new BluesSnapshot(); sn->owner = h; sn->n = h->n;
-        if (hipMalloc((void**)&sn->block, sizeof(double) * 6 * (size_t)h->n) != hipSuccess) { delete sn; E_FAIL(h, "hipMalloc failed"); }
-        for (int k = 0; k < 3; k++) { sn->x[k] = sn->block + (size_t)k * h->n; sn->v[k] = sn->block + (size_t)(3 + k) * h->n; }
-    }
-    sn->has_x = what & 1; sn->has_v = (what & 2) != 0;
-    Copy6Args c; memset(&c, 0, sizeof c);
-    c.n = h->n; c.src_stride = 1; c.dst_stride = 1;
-    if (what & 1) for (int k = 0; k < 3; k++) { c.src[c.count] = h->d_x[k].p; c.dst[c.count++] = sn->x[k]; }
-    if (what & 2) for (int k = 0; k < 3; k++) { c.src[c.count] = h->d_v[k].p; c.dst[c.count++] = sn->v[k]; }
-    hipLaunchKernelGGL(k_copy_arrays, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, c);
-    h->st_launches++;
-    if (h->acc_cache_valid && h->acc_cache_stamp + 1 == h->st_launches) h->acc_cache_stamp = h->st_launches;   // (a copy of x, v does not touch the accumulators)
-    sn->ecache = h->ecache; if (!(what & 1)) sn->ecache.clear();
-    sn->box_epoch = h->box_epoch;
+    BluesSnapshot* sn = snapshot_take(h, what);
+    if (!sn) E_FAIL(h, "hipMalloc failed");
+    hipLaunchKernelGGL(k_copy_arrays, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, make_state_copy_args(h, sn, what, true));
+    snapshot_copy_launched(h);
     HIP_OK(h, hipGetLastError());
     *out = sn;
     return 0;
@@ -4222,20 +4281,24 @@ static int snapshot_usable(BluesEngine* h, const BluesSnapshot* sn) {
     if (sn->owner->device != h->device) E_FAIL(h, "snapshot lives on another device");
     return 0;
 }
+// what a restore of positions does once it goes ahead, before it reads the snapshot
+static int snapshot_positions_begin(BluesEngine* h, const BluesSnapshot* sn) {
+    HIP_OK(h, hipSetDevice(h->device));
+    if (before_position_edit(h)) return 1;
+    if (sn->owner->stream != h->stream) HIP_OK(h, hipStreamSynchronize(sn->owner->stream));   // captured on another engine's stream
+    return 0;
+}
 
 int blues_set_positions_from_snapshot(BluesEngine* h, const BluesSnapshot* sn) {
     if (snapshot_usable(h, sn)) return 1;
     if (!sn->has_x) E_FAIL(h, "the snapshot holds no positions");
-    HIP_OK(h, hipSetDevice(h->device));
-    if (before_position_edit(h)) return 1;
-    if (sn->owner->stream != h->stream) HIP_OK(h, hipStreamSynchronize(sn->owner->stream));   // captured on another engine's stream
+    if (snapshot_positions_begin(h, sn)) return 1;
     if (!h->sorted_ok) {   // never laid out: take the host route once
         std::vector<double> tmp((size_t)3 * h->n);
         if (blues_snapshot_read(const_cast<BluesSnapshot*>(sn), 1, tmp.data(), h->n)) { h->err = sn->owner->err; return 1; }
         return blues_set_positions(h, tmp.data(), h->n);
     }
-    const double* src[3] = {sn->x[0], sn->x[1], sn->x[2]};
-    if (load_positions(h, src, 1, 0)) return 1;
+    if (load_positions(h, sn->x, 1, 0)) return 1;
     h->xfer_foreign = sn->owner != h;
     // the energy that was known for these positions is known again (OpenMM re-evaluates; same value)
     if (sn->owner == h) { if (sn->box_epoch == h->box_epoch) h->ecache = sn->ecache; }   // (not across a change of the box)
@@ -4279,25 +4342,6 @@ static int stage_edit_list(BluesEngine* h, const int32_t* idx, int n_idx, const 
 // array): the unchanged coordinates are restored device to device, the edited ones travel.  Returns 3 (and does nothing)
 // when an edited atom shares a constraint cluster with an atom that is not edited -- the cluster would have to be made
 // whole with coordinates only the device has; the caller then takes the plain host route.
-// the general clusters' part of the rule above: 3 if an edited atom shares a general cluster with one that is not edited, else every
-// edited general cluster is made one periodic image (pos_of: place in the edit list or -1; ed: its coordinates)
-static int gen_edit_whole(const BluesEngine* h, const std::vector<int>& pos_of, double* ed) {
-    size_t t = 0;
-    for (const GenCluster& G : h->gen_h) {
-        int inside = 0;
-        for (int a = 0; a < G.na; a++) inside += pos_of[h->gen_atoms_h[G.a0 + a].atom] >= 0;
-        const size_t t1 = t + 2 * (size_t)(G.na - 1);
-        if (inside != 0 && inside != G.na) return 3;
-        if (inside) for (size_t q = t; q < t1; q += 2)
-            for (int k = 0; k < 3; k++) {
-                const double d = ed[3 * pos_of[h->gen_tree[q]] + k] - ed[3 * pos_of[h->gen_tree[q + 1]] + k];
-                ed[3 * pos_of[h->gen_tree[q]] + k] -= lattice_shift(h, k, d);
-            }
-        t = t1;
-    }
-    return 0;
-}
-
 int blues_set_positions_from_snapshot_edited(BluesEngine* h, const BluesSnapshot* sn, const int32_t* idx, int32_t n_idx, const double* xyz) {
     if (snapshot_usable(h, sn)) return 1;
     if (!sn->has_x) E_FAIL(h, "the snapshot holds no positions");
@@ -4306,24 +4350,10 @@ int blues_set_positions_from_snapshot_edited(BluesEngine* h, const BluesSnapshot
     std::vector<int> pos_of(h->n, -1);
     for (int e = 0; e < n_idx; e++) { if (idx[e] < 0 || idx[e] >= h->n) E_FAIL(h, "edited atom %d out of range", idx[e]); pos_of[idx[e]] = e; }
     std::vector<double> ed(xyz, xyz + 3 * (size_t)n_idx);
-    for (const HostCluster& c : h->clusters) {
-        int inside = 0, total = 0;
-        for (int a = 0; a < 4; a++) if (c.atoms[a] >= 0) { total++; inside += pos_of[c.atoms[a]] >= 0; }
-        if (inside == 0) continue;
-        if (inside != total) return 3;
-        for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0)   // one whole periodic image per cluster, as blues_set_positions stores them
-            for (int k = 0; k < 3; k++) {
-                const double d = ed[3 * pos_of[c.atoms[a]] + k] - ed[3 * pos_of[c.atoms[0]] + k];
-                ed[3 * pos_of[c.atoms[a]] + k] -= lattice_shift(h, k, d);
-            }
-    }
-    if (gen_edit_whole(h, pos_of, ed.data())) return 3;
-    HIP_OK(h, hipSetDevice(h->device));
-    if (before_position_edit(h)) return 1;
-    if (sn->owner->stream != h->stream) HIP_OK(h, hipStreamSynchronize(sn->owner->stream));
+    if (clusters_whole(h, ed.data(), pos_of.data())) return 3;   // (one whole periodic image per cluster, as blues_set_positions stores them)
+    if (snapshot_positions_begin(h, sn)) return 1;
     if (stage_edit_list(h, idx, n_idx, ed.data())) return 1;
-    const double* src[3] = {sn->x[0], sn->x[1], sn->x[2]};
-    if (load_positions(h, src, 1, n_idx)) return 1;
+    if (load_positions(h, sn->x, 1, n_idx)) return 1;
     if (sn->owner != h && resolve_xfer(h)) return 1;
     return 0;
 }
@@ -4352,11 +4382,8 @@ int blues_set_velocities_from_snapshot(BluesEngine* h, const BluesSnapshot* sn) 
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
     if (sn->owner->stream != h->stream) HIP_OK(h, hipStreamSynchronize(sn->owner->stream));
-    Copy6Args c; memset(&c, 0, sizeof c);
-    c.n = h->n; c.count = 3; c.src_stride = 1; c.dst_stride = 1;
-    for (int k = 0; k < 3; k++) { c.src[k] = sn->v[k]; c.dst[k] = h->d_v[k].p; }
-    hipLaunchKernelGGL(k_copy_arrays, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, c);
-    h->st_launches++; h->vel_clean = false; h->ke_cache_valid = false;
+    hipLaunchKernelGGL(k_copy_arrays, dim3((h->n + 255) / 256), dim3(256), 0, h->stream, make_state_copy_args(h, sn, 2, false));
+    h->st_launches++; velocities_replaced(h);
     HIP_OK(h, hipGetLastError());
     if (sn->owner->stream != h->stream) HIP_OK(h, hipStreamSynchronize(h->stream));   // the owner may recycle the buffer on its own stream
     return 0;
@@ -4514,21 +4541,10 @@ int blues_batch_snapshot_capture(BluesBatch* B, int32_t what, const int32_t* mas
         // (a failure half way through: the snapshots already taken for earlier members go back to their owners' pools)
         auto undo = [&]() { for (int q = 0; q < r; q++) if (out[q]) { out[q]->owner->snap_pool.push_back(out[q]); out[q] = nullptr; } };
         if ((what & 1) && !h->have_positions) { undo(); B->err = "positions have not been set"; batch_leave(B); return 1; }
-        BluesSnapshot* sn = nullptr;
-        if (!h->snap_pool.empty()) { sn = h->snap_pool.back(); h->snap_pool.pop_back(); }
-        else {
-            sn = new BluesSnapshot(); sn->owner = h; sn->n = h->n;
-            if (hipMalloc((void**)&sn->block, sizeof(double) * 6 * (size_t)h->n) != hipSuccess) { delete sn; undo(); B->err = "hipMalloc failed"; batch_leave(B); return 1; }
-            for (int k = 0; k < 3; k++) { sn->x[k] = sn->block + (size_t)k * h->n; sn->v[k] = sn->block + (size_t)(3 + k) * h->n; }
-        }
-        sn->has_x = what & 1; sn->has_v = (what & 2) != 0;
-        c.n = h->n; c.src_stride = 1; c.dst_stride = 1;
-        if (what & 1) for (int k = 0; k < 3; k++) { c.src[c.count] = h->d_x[k].p; c.dst[c.count++] = sn->x[k]; }
-        if (what & 2) for (int k = 0; k < 3; k++) { c.src[c.count] = h->d_v[k].p; c.dst[c.count++] = sn->v[k]; }
-        sn->ecache = h->ecache; if (!(what & 1)) sn->ecache.clear();
-        sn->box_epoch = h->box_epoch;
-        h->st_launches++;
-        if (h->acc_cache_valid && h->acc_cache_stamp + 1 == h->st_launches) h->acc_cache_stamp = h->st_launches;   // (a copy of x, v does not touch the accumulators)
+        BluesSnapshot* sn = snapshot_take(h, what);
+        if (!sn) { undo(); B->err = "hipMalloc failed"; batch_leave(B); return 1; }
+        c = make_state_copy_args(h, sn, what, true);
+        snapshot_copy_launched(h);
         out[r] = sn;
     }
     int rc = batch_arena_upload(B, sizeof(Copy6Args) * R);
@@ -4557,22 +4573,8 @@ static int batch_restore_impl(BluesBatch* B, BluesSnapshot* const* snaps, int wh
             std::vector<int> pos_of(n, -1);
             for (int e = 0; e < n_idx; e++) { if (idx[e] < 0 || idx[e] >= n) { B->err = "edited atom out of range"; return 1; } pos_of[idx[e]] = e; }
             ed.assign(xyz, xyz + (size_t)3 * n_idx * R);
-            for (int r = 0; r < R; r++) if (snaps[r]) {
-                BluesEngine* h = B->eng[r];
-                double* e0 = ed.data() + (size_t)3 * n_idx * r;
-                for (const HostCluster& c : h->clusters) {
-                    int inside = 0, total = 0;
-                    for (int a = 0; a < 4; a++) if (c.atoms[a] >= 0) { total++; inside += pos_of[c.atoms[a]] >= 0; }
-                    if (inside == 0) continue;
-                    if (inside != total) return 3;
-                    for (int a = 1; a < 4; a++) if (c.atoms[a] >= 0)
-                        for (int k = 0; k < 3; k++) {
-                            const double d = e0[3 * pos_of[c.atoms[a]] + k] - e0[3 * pos_of[c.atoms[0]] + k];
-                            e0[3 * pos_of[c.atoms[a]] + k] -= lattice_shift(h, k, d);
-                        }
-                }
-                if (gen_edit_whole(h, pos_of, e0)) return 3;
-            }
+            for (int r = 0; r < R; r++) if (snaps[r])
+                if (clusters_whole(B->eng[r], ed.data() + (size_t)3 * n_idx * r, pos_of.data())) return 3;
         }
     }
     if (what & 2) for (int r = 0; r < R; r++) if (snaps[r] && (snapshot_usable(B->eng[r], snaps[r]) || !snaps[r]->has_v)) { B->err = "the snapshot holds no velocities"; return 1; }
@@ -4597,19 +4599,11 @@ static int batch_restore_impl(BluesBatch* B, BluesSnapshot* const* snaps, int wh
         if (!snaps[r]) continue;
         const BluesSnapshot* sn = snaps[r];
         if (what & 1) {
-            a.n = h->n; a.stride = 1;
-            for (int k = 0; k < 3; k++) { a.src[k] = sn->x[k]; a.x[k] = h->d_x[k].p; a.x_sort[k] = h->d_x_sort[k].p; }
-            a.mass = h->d_mass.p; a.alch_local = h->d_alch_local.p; a.sorted_of_orig = h->d_sorted_of_orig.p;
-            a.img_f = h->precision == 0 ? h->d_img_f.p : nullptr; a.img_d = h->precision == 0 ? nullptr : h->d_img_d.p;
-            a.box = make_box(h); a.out = h->d_xfer_out.p;
+            a = make_load_args(h, sn->x, 1);
             a.keep_out = h->xfer_pending ? 1 : 0;   // (a verdict still pending from an earlier load is kept: the kernels only OR / max / add into it)
-            if (n_idx > 0) {
-                e.n_edit = n_idx; e.idx = reinterpret_cast<const int*>(dbase + off_idx); e.xyz = reinterpret_cast<const double*>(dbase + off_xyz) + (size_t)3 * n_idx * r;
-                for (int k = 0; k < 3; k++) { e.x[k] = h->d_x[k].p; e.x_sort[k] = h->d_x_sort[k].p; }
-                e.mass = a.mass; e.alch_local = a.alch_local; e.sorted_of_orig = a.sorted_of_orig; e.img_f = a.img_f; e.img_d = a.img_d; e.box = a.box; e.out = a.out;
-            }
+            if (n_idx > 0) e = make_edit_args(h, a, n_idx, reinterpret_cast<const int*>(dbase + off_idx), reinterpret_cast<const double*>(dbase + off_xyz) + (size_t)3 * n_idx * r);
         }
-        if (what & 2) { c.n = h->n; c.count = 3; c.src_stride = 1; c.dst_stride = 1; for (int k = 0; k < 3; k++) { c.src[k] = sn->v[k]; c.dst[k] = h->d_v[k].p; } }
+        if (what & 2) c = make_state_copy_args(h, sn, 2, false);
     }
     int rc = batch_arena_upload(B, total);
     const LoadPosArgs* dla = reinterpret_cast<const LoadPosArgs*>(dbase + off_load);
@@ -4628,12 +4622,12 @@ static int batch_restore_impl(BluesBatch* B, BluesSnapshot* const* snaps, int wh
         BluesEngine* h = B->eng[r];
         if (what & 1) {
             h->xfer_pending = true; h->xfer_stream = h->stream; h->xfer_src = B->h_xfer_all + 4 * r; h->xfer_foreign = snaps[r]->owner != h;
-            h->have_positions = true; h->x_edited = true; h->led_open = false; h->led_dirty = false; h->pass_valid = false; h->fin_pending = false; h->ecache.clear(); h->lists_forced = true;
+            positions_replaced(h);
             h->st_launches += n_idx > 0 ? 2 : 1;
             if (snaps[r]->owner == h && n_idx == 0 && snaps[r]->box_epoch == h->box_epoch) h->ecache = snaps[r]->ecache;   // the energy that was known for these positions (in this box) is known again
             if (resolve_xfer(h)) { B->err = h->err; return 1; }   // (already on the host: no wait)
         }
-        if (what & 2) { h->st_launches++; h->vel_clean = false; h->ke_cache_valid = false; }
+        if (what & 2) { h->st_launches++; velocities_replaced(h); }
     }
     return 0;
 }
@@ -4692,8 +4686,8 @@ int blues_batch_reset(BluesBatch* B, const int32_t* mask) {
         acc[r] = nullptr;
         if (mask && !mask[r]) continue;
         acc[r] = h->d_acc.p;
-        h->h_step = 0; h->h_lambda = 0.0; h->h_first_step = 0; h->h_perturbed = 0.0; h->h_unperturbed = 0.0; h->h_prop = 1; h->h_lambda_step = 0;
-        h->unpert_valid = false; h->x_edited = false; h->pass_valid = false; h->fin_pending = false; h->acc_cache_valid = false; h->led_open = false; h->led_dirty = false;
+        protocol_rewound(h);
+        h->acc_cache_valid = false; h->led_open = false; h->led_dirty = false;
     }
     int rc = batch_arena_upload(B, sizeof(DevAccum*) * R);
     if (!rc) hipLaunchKernelGGL(k_zero_acc_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, reinterpret_cast<DevAccum* const*>(B->d_arena.p), R);
@@ -4718,7 +4712,7 @@ int blues_batch_set_velocities_to_temperature(BluesBatch* B, double temperature,
         if (mask && !mask[r]) continue;
         a.n = h->n; a.mass = h->d_mass.p; for (int k = 0; k < 3; k++) a.v[k] = h->d_v[k].p;
         a.kT = KB_KJ * temperature; a.seed = (unsigned long long)seeds[r]; a.stream = (unsigned)h->replica * 4u + 1u;
-        h->st_launches++; h->vel_clean = false; h->ke_cache_valid = false;
+        h->st_launches++; velocities_replaced(h);
     }
     int rc = batch_arena_upload(B, sizeof(MaxwellArgs) * R);
     if (!rc) hipLaunchKernelGGL(k_maxwell_b, dim3((batch_max_n(B) + 255) / 256, R), dim3(256), 0, B->stream, reinterpret_cast<const MaxwellArgs*>(B->d_arena.p));

@@ -893,6 +893,102 @@ def test_batched_plugin_boundary_equals_chain_by_chain(Engine, tol_box, tune):
     assert st1["fallback_steps"] <= st0["fallback_steps"]
 
 
+def test_edited_restore_takes_whole_constraint_clusters_only(Engine, tol_box, tune):
+    """setPositions of a State in which a Move changed a few atoms, lone (blues_set_positions_from_snapshot_edited) and for all chains
+    at once (blues_batch_restore_edited).  An edit list that holds one hydrogen of a water splits a constraint cluster: both routes
+    decline (False) and leave positions and energy of every chain as they were, bit for bit.  An edit list of whole clusters (the
+    ligand and one water, put across a box face with its atoms wrapped one by one into the box) is applied, and the lone route, the
+    batched route and set_positions(full array) on a third set of engines store the same coordinates -- the water as one periodic
+    image -- and stay together, bit for bit, over further steps."""
+    from blues_amd.engine import NativeBatch
+    s, v = tol_box
+    R, n_before, n_after = 3, 4, 4
+    tune(assume_batch=R)
+    vels = _replica_inputs(s, v, R)
+    lig = np.arange(15)
+    lone, members, host = (_make(Engine, s, vels, 16, 0) for _ in range(3))
+    batch = NativeBatch(members)
+    box = np.diag(lone[0].get_box())
+    try:
+        for g in lone + host:
+            g.step(n_before)
+        batch.step(n_before)
+        x = [g.get_positions() for g in lone]
+        for r in range(R):
+            assert np.array_equal(members[r].get_positions(), x[r]) and np.array_equal(host[r].get_positions(), x[r]), r
+        # the water whose oxygen is nearest to a box face (chain 0 decides which, and along which axis)
+        oxygens = np.arange(15, s.n_atoms, 3)
+        assert np.all(s.mass[oxygens] > 10.0) and np.all(s.mass[oxygens + 1] < 4.0) and np.all(s.mass[oxygens + 2] < 4.0)   # (O, H, H; repartitioned masses)
+        frac = np.mod(x[0][oxygens], box)
+        dist = np.minimum(frac, box - frac)
+        w, axis = np.unravel_index(np.argmin(dist), dist.shape)
+        water = oxygens[w] + np.arange(3)
+
+        # ---- one hydrogen of that water: the cluster would be split, nothing is done
+        e_before = [[g.potential_energy() for g in gs] for gs in (lone, members, host)]   # (host too: all three sets go through the same calls)
+        part = water[1:2]
+        moved = [x[r][part] + np.array([0.001, 0.0, 0.0]) for r in range(R)]
+        for r in range(R):
+            snap = lone[r].snapshot(positions=True, velocities=False)
+            assert lone[r].set_positions_from_snapshot_edited(snap, part, moved[r]) is False
+            snap.release()
+        snaps = batch.snapshot_all(positions=True, velocities=False)
+        assert batch.restore_edited_all(snaps, part, np.stack(moved)) is False
+        for sn in snaps:
+            sn.release()
+        for gs, es in zip((lone, members, host), e_before):
+            for r in range(R):
+                assert np.array_equal(gs[r].get_positions(), x[r]), r
+                assert gs[r].potential_energy() == es[r], r
+
+        # ---- the whole water and the ligand
+        idx = np.concatenate([lig, water])
+        rot = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+        new = []
+        for r in range(R):
+            l = x[r][lig]
+            l = (l - l.mean(0)) @ rot.T + l.mean(0)
+            f = np.mod(x[r][water[0], axis], box[axis])
+            shift = np.zeros(3); shift[axis] = -f if f < box[axis] - f else box[axis] - f   # the oxygen onto the nearest face
+            new.append(np.concatenate([l, np.mod(x[r][water] + shift, box)]))                # every atom into the box on its own
+        side = [np.mod(new[r][15:, axis] + 0.5 * box[axis], box[axis]) - 0.5 * box[axis] for r in range(R)]
+        assert all(sd.min() < 0.0 < sd.max() or (sd == 0.0).any() for sd in side)           # (the water lies across the face)
+        assert any(np.ptp(new[r][15:, axis]) > 0.5 * box[axis] for r in range(R))            # (and its atoms arrive as different images)
+        for r in range(R):
+            snap = lone[r].snapshot(positions=True, velocities=False)
+            assert lone[r].set_positions_from_snapshot_edited(snap, idx, new[r]) is True
+            snap.release()
+        snaps = batch.snapshot_all(positions=True, velocities=False)
+        assert batch.restore_edited_all(snaps, idx, np.stack(new)) is True
+        for sn in snaps:
+            sn.release()
+        for r in range(R):
+            full = x[r].copy(); full[idx] = new[r]
+            host[r].set_positions(full)
+
+        def same(r):
+            a, b, c = lone[r], members[r], host[r]
+            xa, va = a.get_positions(), a.get_velocities()
+            return (np.array_equal(xa, b.get_positions()) and np.array_equal(xa, c.get_positions())
+                    and np.array_equal(va, b.get_velocities()) and np.array_equal(va, c.get_velocities())
+                    and a.get_global("protocol_work") == b.get_global("protocol_work") == c.get_global("protocol_work"))
+        for r in range(R):
+            assert same(r), r
+            xr = lone[r].get_positions()
+            assert np.ptp(xr[water, axis]) < 0.2                                             # stored as one periodic image
+            rest = np.setdiff1d(np.arange(s.n_atoms), idx)
+            assert np.array_equal(xr[rest], x[r][rest]) and np.array_equal(xr[lig], new[r][:15])
+        for g in lone + host:
+            g.step(n_after)
+        batch.step(n_after)
+        for r in range(R):
+            assert same(r), r
+    finally:
+        batch.close()
+        for g in lone + members + host:
+            g.close()
+
+
 def test_two_batches_taking_turns_on_the_device_equal_the_batches_run_one_after_the_other(Engine, tol_box, tune):
     """Several BatchedBLUESSimulation objects on one GPU, each driven from its own host thread, sharing a `device_turn` lock
     (bench.py --groups): the stepping calls take turns on the device, the host phases overlap them.  Chains are independent and
