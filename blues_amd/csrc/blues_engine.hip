@@ -33,6 +33,7 @@
 #include <thread>
 #include <functional>
 #include <atomic>
+#include <type_traits>
 #include "kernels_integrate.h"
 #include "kernels_nb.h"
 #include "kernels_pme.h"
@@ -448,6 +449,15 @@ static inline bool batch_dry(const BluesEngine* h) { return h->batch && h->batch
 static inline bool batch_lead(const BluesEngine* h) { return h->batch && h->batch->lockstep && h->batch->leader == h; }
 static inline int* batch_req_ptr(const BluesEngine* h) { return h->batch && h->batch->sync_lists ? h->batch->d_req.p : nullptr; }
 template <typename R> static const RepNb<R>* batch_reps_nb(const BluesBatch* b) { if constexpr (sizeof(R) == 4) return b->d_nb_f.p; else return b->d_nb_d.p; }
+template <typename R> static auto engine_img(const BluesEngine* h) { if constexpr (sizeof(R) == 4) return h->d_img_f.p; else return h->d_img_d.p; }
+// One of two instantiations, chosen at run time: f is a generic lambda that is handed a value of the chosen tag type (a precision:
+// `using T = decltype(tag)`; a template flag: std::true_type / std::false_type).  by_precision: float for mixed precision, else double.
+template <typename A, typename B, typename F> static auto pick_tag(bool first, F&& f) { if (first) return f(A()); else return f(B()); }
+template <typename F> static auto by_precision(int precision, F&& f) { return pick_tag<float, double>(precision == 0, f); }
+static inline bool member_in_call(const BluesBatch* B, int r) { return B->active[r] && !B->failed[r]; }   // the member sets of a batched call.  This one: takes part in this call
+static inline bool member_stepping(const BluesBatch* B, int r) { return !B->failed[r]; }   // still stepping (batch_do_steps starts masked members out as failed)
+static inline bool member_shared(const BluesBatch* B, int r) { return !B->failed[r] && !B->eng[r]->straggler; }   // in the shared launches (a straggler issues its own)
+static inline bool member_in_lockstep(const BluesBatch* B, int r) { return member_shared(B, r) && !B->eng[r]->solo_now; }   // ... and not out of step for this phase
 
 static inline bool nocut(const BluesEngine* h) { return h->nb_method == BLUES_NB_NOCUTOFF; }
 // NoCutoff: a box that does not wrap (L = invL = 0: min_image_d returns the difference itself), whatever box is stored -- zero included
@@ -2316,6 +2326,14 @@ static int force_pass(BluesEngine* h, int base_L) {
     return 0;
 }
 
+// the longest outer and inner row of the fragment lists (one download each); false, and nothing written, when a download failed
+static bool frag_longest_rows(const BluesEngine* h, int* outer, int* inner) {
+    std::vector<int> oc, ic;
+    try { h->d_ocount.download(oc); h->d_icount.download(ic); } catch (std::string&) { return false; }
+    *outer = *inner = 0;
+    for (int q = 0; q < h->frag_NI; q++) { if (q < (int)oc.size()) *outer = std::max(*outer, oc[q]); if (q < (int)ic.size()) *inner = std::max(*inner, ic[q]); }
+    return true;
+}
 static int check_flags(BluesEngine* h) {
     HIP_OK(h, hipStreamSynchronize(h->stream));
     DevFlags f;
@@ -2336,9 +2354,7 @@ static int check_flags(BluesEngine* h) {
     }
     if (f.list_overflow && h->k1_mode == 3 && (f.list_overflow & ~1)) {
         int mo = -1, mi = -1;
-        try { std::vector<int> oc, ic; h->d_ocount.download(oc); h->d_icount.download(ic); mo = mi = 0;
-              for (int q = 0; q < h->frag_NI && q < (int)oc.size(); q++) mo = std::max(mo, oc[q]);
-              for (int q = 0; q < h->frag_NI && q < (int)ic.size(); q++) mi = std::max(mi, ic[q]); } catch (std::string&) {}
+        frag_longest_rows(h, &mo, &mi);   // (a failed download: the message says -1)
         E_FAIL(h, "neighbour list capacity exceeded (fragment lists:%s%s%s%s; longest outer row %d of %d, inner %d of %d; %d fragments)",
                (f.list_overflow & FR_OVER_OUTER) ? " outer rows" : "", (f.list_overflow & FR_OVER_INNER) ? " inner rows" : "",
                (f.list_overflow & FR_OVER_QUEUE) ? " the builder's candidate queue" : "", (f.list_overflow & FR_OVER_REACH) ? " a fragment's reach against the box" : "",
@@ -2358,11 +2374,8 @@ static int check_flags(BluesEngine* h) {
 // gave them (a solute-rich region, a denser phase): then the next layout gets a quarter more -- before an entry is ever dropped.
 static void frag_grow_caps(BluesEngine* h) {
     if (h->k1_mode != 3 || h->frag_NI <= 0) return;
-    std::vector<int> oc, ic;
-    try { h->d_ocount.download(oc); h->d_icount.download(ic); } catch (std::string&) { return; }
     int mo = 0, mi = 0;
-    for (int q = 0; q < h->frag_NI && q < (int)oc.size(); q++) mo = std::max(mo, oc[q]);
-    for (int q = 0; q < h->frag_NI && q < (int)ic.size(); q++) mi = std::max(mi, ic[q]);
+    if (!frag_longest_rows(h, &mo, &mi)) return;
     if (h->frag_ocap <= h->frag_F && (100 * mo > 85 * h->frag_ocap || mo > h->frag_ocap - 64)) h->frag_grow_o *= 1.25;   // (a row of F + 1 places holds every fragment)
     if (h->frag_icap <= h->frag_F && (100 * mi > 85 * h->frag_icap || mi > h->frag_icap - 64)) h->frag_grow_i *= 1.25;
     if (h->tune.debug_lists) fprintf(stderr, "[frag caps] member %d: longest outer row %d of %d, inner %d of %d; growth %.2f / %.2f\n", h->batch_index, mo, h->frag_ocap, mi, h->frag_icap, h->frag_grow_o, h->frag_grow_i);
@@ -2388,13 +2401,15 @@ static int poll_resort_due(BluesEngine* h) {
 // what the lone chain does -- comes due for all members of a batch at the same poll, where the host's cores share them.
 #define RESORT_AGE 4096
 static bool resort_by_age(const BluesEngine* h) { return h->k1_mode == 3 && h->sorted_ok && 2 * h->mobile.size() > (size_t)h->n && h->steps_since_sort >= RESORT_AGE; }
-static int poll_resort(BluesEngine* h) {
+// 1: the engine is to be laid out again, by age or because its builder asked (counted either way); 0: no; -1: error
+static int resort_wanted(BluesEngine* h) {
     const bool aged = resort_by_age(h);
     const int due = poll_resort_due(h);   // (clears a pending hint and gives the lists more room where they ask: also when the age brings the re-sort anyway)
-    if (due < 0) return 1;
+    if (due < 0) return -1;
     if (aged && !due) h->st_resorts++;
-    return (aged || due) ? relayout(h) : 0;
+    return aged || due;
 }
+static int poll_resort(BluesEngine* h) { const int want = resort_wanted(h); return want < 0 ? 1 : (want ? relayout(h) : 0); }
 
 // launch geometry of an energy evaluation (partials per kind)
 struct EnergyShape { int nw, nbb, nfb; size_t off_frozen; };
@@ -2431,12 +2446,11 @@ static int energy_launch(BluesEngine* h) {
     if (launch_pme(h, 1)) return 1;
     const EnergyShape g = energy_shape(h);
     if (g.nbb > 0) {
-        if (h->n_cent > 0) {
-            if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b<true>, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
-            else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy<true>, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
-        }
-        else if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b<false>, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
-        else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy<false>, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
+        pick_tag<std::true_type, std::false_type>(h->n_cent > 0, [&](auto cent) {   // (with / without centroid bonds)
+            constexpr bool CENT = decltype(cent)::value;
+            if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b<CENT>, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
+            else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy<CENT>, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
+        });
         h->st_launches++;
     }
     HIP_OK(h, hipGetLastError());
@@ -2478,13 +2492,11 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
     if (nocut(h)) { h->e_frozen[0] = h->e_frozen[1] = 0.0; h->e_frozen_valid = true; }   // (its partial slab has no room for the frozen kernels' output, nor any use for it)
     if (!h->e_frozen_valid) {
         double* ep = h->d_epart_nb.p + g.off_frozen;
-        if (h->precision == 0) {
-            hipLaunchKernelGGL(k_frozen_boxes<float>, dim3((g.nfb + 3) / 4), dim3(256), 0, h->stream, h->n, make_nbconst<float>(h), h->d_img_f.p, ep);
-            hipLaunchKernelGGL(k_energy_frozen<float>, dim3(g.nfb), dim3(256), 0, h->stream, h->n, make_nbconst<float>(h), h->d_img_f.p, h->d_ex_start.p, h->d_ex_idx.p, ep);
-        } else {
-            hipLaunchKernelGGL(k_frozen_boxes<double>, dim3((g.nfb + 3) / 4), dim3(256), 0, h->stream, h->n, make_nbconst<double>(h), h->d_img_d.p, ep);
-            hipLaunchKernelGGL(k_energy_frozen<double>, dim3(g.nfb), dim3(256), 0, h->stream, h->n, make_nbconst<double>(h), h->d_img_d.p, h->d_ex_start.p, h->d_ex_idx.p, ep);
-        }
+        by_precision(h->precision, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(k_frozen_boxes<T>, dim3((g.nfb + 3) / 4), dim3(256), 0, h->stream, h->n, make_nbconst<T>(h), engine_img<T>(h), ep);
+            hipLaunchKernelGGL(k_energy_frozen<T>, dim3(g.nfb), dim3(256), 0, h->stream, h->n, make_nbconst<T>(h), engine_img<T>(h), h->d_ex_start.p, h->d_ex_idx.p, ep);
+        });
         h->st_launches += 2;
     }
     if (check_flags(h)) return 1;
@@ -2546,8 +2558,7 @@ static int ledger_pe(BluesEngine* h, int close) {
     L.nw = g.nw; L.nbb = g.nbb; L.PA = h->PA; L.k2_jiter = h->k2_jiter; L.k2_nblocks_env = h->k2_nblocks_env; L.le = h->cur_le;
     L.acc = h->d_acc.p; L.close = close;
     if (batch_lead(h)) {
-        if (h->precision == 0) hipLaunchKernelGGL(k_ledger_pe_b<float>, dim3(h->batch->R()), dim3(64), 0, h->cur, h->batch->d_nb_f.p, h->batch->d_core.p, L);
-        else hipLaunchKernelGGL(k_ledger_pe_b<double>, dim3(h->batch->R()), dim3(64), 0, h->cur, h->batch->d_nb_d.p, h->batch->d_core.p, L);
+        by_precision(h->precision, [&](auto tag) { using T = decltype(tag); hipLaunchKernelGGL(k_ledger_pe_b<T>, dim3(h->batch->R()), dim3(64), 0, h->cur, batch_reps_nb<T>(h->batch), h->batch->d_core.p, L); });
     } else if (!batch_dry(h)) hipLaunchKernelGGL(k_ledger_pe, dim3(1), dim3(64), 0, h->cur, L);
     h->st_launches++; h->acc_cache_valid = false;
     HIP_OK(h, hipGetLastError());
@@ -2888,8 +2899,8 @@ static bool batch_congruent_cached(BluesBatch* B, int r, const BluesEngine* lead
 static int batch_refresh_args(BluesBatch* B) {
     bool dirty = false;
     BluesEngine* lead = B->leader ? B->leader : B->eng[0];
-    for (int r = 0; r < B->R(); r++) dirty |= B->seen_epoch[r] != B->eng[r]->args_epoch || B->rec_active[r] != (char)(B->active[r] && !B->failed[r] && !B->eng[r]->straggler && !B->eng[r]->solo_now)
-                                              || (!B->failed[r] && B->rec_delta[r] != B->eng[r]->h_draw - lead->h_draw);
+    for (int r = 0; r < B->R(); r++) dirty |= B->seen_epoch[r] != B->eng[r]->args_epoch || B->rec_active[r] != (char)(B->active[r] && member_in_lockstep(B, r))
+                                              || (member_stepping(B, r) && B->rec_delta[r] != B->eng[r]->h_draw - lead->h_draw);
     if (!dirty) return 0;
     const double one[3] = {1.0, 1.0, 1.0};
     std::vector<RepCore> core(B->R()); std::vector<RepNb<float>> nf; std::vector<RepNb<double>> nd;
@@ -2899,7 +2910,7 @@ static int batch_refresh_args(BluesBatch* B) {
     if (single) nf.resize(B->R()); else nd.resize(B->R());
     for (int r = 0; r < B->R(); r++) {
         BluesEngine* h = B->eng[r];
-        B->rec_active[r] = (char)(B->active[r] && !B->failed[r] && !h->straggler && !h->solo_now);   // (a straggler's kernels are its own: the shared launches pass it by)
+        B->rec_active[r] = (char)(B->active[r] && member_in_lockstep(B, r));   // (a straggler's kernels are its own: the shared launches pass it by)
         core[r].active = B->rec_active[r];
         B->rec_delta[r] = h->h_draw - lead->h_draw; core[r].draw_delta = B->rec_delta[r];
         if (single) nf[r].active = B->rec_active[r]; else nd[r].active = B->rec_active[r];
@@ -2918,6 +2929,141 @@ static int batch_refresh_args(BluesBatch* B) {
     return 0;
 }
 
+// The way into a shared section: the members issue into the batch's stream, `lead` leads, the device records are current.  The caller
+// leaves again (batch_leave) unless the batch had been entered before it came.  (B->entered false afterwards: batch_enter failed.)
+static int batch_section_begin(BluesBatch* B, BluesEngine* lead) { if (batch_enter(B)) return 1; B->leader = lead; return batch_refresh_args(B); }
+// f(r) for the members r that `in` admits: in lock step (the leader's launches serve them all: batch_lead / batch_dry) or, lockstep
+// false, each on launches of its own.  Stops at the first member for which f returns non-zero and returns its index; -1: none did.
+template <typename In, typename F> static int batch_each(BluesBatch* B, bool lockstep, In in, F f) {
+    int bad = -1; B->lockstep = lockstep;
+    for (int r = 0; r < B->R() && bad < 0; r++) if (in(r) && f(r)) bad = r;
+    B->lockstep = false; return bad;
+}
+// The one gather of the members' flag summaries (bit 0: the list builder asks for a new order, bit 1: an error flag is up; an inactive
+// record answers 0: k_gather_hints_b).  Both halves throw a std::string where a buffer or the copy fails; what that means is the caller's.
+static void batch_launch_hints(BluesBatch* B) {
+    if ((int)B->d_hints.n != B->R()) B->d_hints.alloc(B->R());
+    hipLaunchKernelGGL(k_gather_hints_b, dim3((B->R() + 255) / 256), dim3(256), 0, B->stream, B->d_core.p, B->R(), B->d_hints.p);
+}
+static void batch_read_hints(const BluesBatch* B, std::vector<int>& hints) { B->d_hints.download(hints); }   // (after the caller's synchronisation)
+static int batch_gather_hints(BluesBatch* B, std::vector<int>& hints) { batch_launch_hints(B); if (hipStreamSynchronize(B->stream) != hipSuccess) return 1; batch_read_hints(B, hints); return 0; }   // launch, wait, read.  1: the synchronisation failed (B->err is left alone)
+// ---- batch_prefetch, pass by pass.  live[r]: member r takes part in the batched evaluation; a pass answers false when something failed.
+// A few members whose State arrived far from where their tiles were laid out (a restore after a re-sort at a poll: resolve_xfer) have
+// no layout now.  They are laid out HERE: left as they were, the check in batch_prefetch sent ALL members to their own on-demand evaluation --
+// 1024 lone energy evaluations, 0.15-0.25 s, in an iteration that names no layout event (round 6: three such iterations in 40 runs).
+static int prefetch_lay_out(BluesBatch* B) {
+    auto placed = [&](int r) { return member_in_call(B, r) && B->eng[r]->have_positions && !B->eng[r]->straggler; };
+    int lacking = 0, have = 0;
+    for (int r = 0; r < B->R(); r++) if (placed(r)) { have++; lacking += !B->eng[r]->sorted_ok; }
+    if (lacking == 0 || lacking > std::max(1, have / 8) || B->lockstep) return 0;
+    if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
+    for (int r = 0; r < B->R(); r++) if (placed(r) && !B->eng[r]->sorted_ok) { if (ensure_sorted(B->eng[r])) B->failed[r] = 1; B->st_relayouts++; }
+    return 0;
+}
+// fills live[]; returns the first live member, who leads (null: none)
+static BluesEngine* prefetch_live(const BluesBatch* B, std::vector<char>& live) {
+    live.assign(B->R(), 0);
+    for (int r = 0; r < B->R(); r++) live[r] = member_in_call(B, r) && B->eng[r]->have_positions && B->eng[r]->sorted_ok && !B->eng[r]->straggler;   // (a straggler evaluates on demand, with launches of its own)
+    for (int r = 0; r < B->R(); r++) if (live[r]) return B->eng[r];
+    return nullptr;
+}
+// The frozen-frozen constant of the members that have none.  One member (a chain that joined late): its own evaluation.
+// Several -- every chain of a batch whose State came from the MD leg, in every iteration: the frozen atoms were given new
+// positions -- in one launch over a work list; member by member this was a full lone energy evaluation with its host
+// synchronisations each, 0.7 s per 1024 chains and iteration (half of the NCMC leg of a real run)
+static bool prefetch_frozen(BluesBatch* B, BluesEngine* lead, std::vector<char>& live) {
+    std::vector<int> lack;
+    for (int r = 0; r < B->R(); r++) if (live[r] && !B->eng[r]->e_frozen_valid && !nocut(B->eng[r])) lack.push_back(r);
+    bool together = lack.size() > 1;
+    for (size_t q = 0; q < lack.size() && together; q++) { const char* why = ""; together = batch_congruent_cached(B, lack[q], lead, &why) && B->eng[lack[q]]->prog.n == 0; }
+    if (!together) { for (int r : lack) { double E; if (total_energy(B->eng[r], &E)) { B->failed[r] = 1; live[r] = 0; } } return true; }
+    if (batch_section_begin(B, lead)) return false;
+    const int R = B->R(), count = (int)lack.size(); const EnergyShape g = energy_shape(lead);
+    std::vector<double> sums;
+    try {
+        if ((int)B->d_frozen_work.n < count) B->d_frozen_work.alloc(R);
+        if ((int)B->d_frozen_sum.n < 2 * count) B->d_frozen_sum.alloc((size_t)2 * R);
+        if (hipMemcpyAsync(B->d_frozen_work.p, lack.data(), sizeof(int) * count, hipMemcpyHostToDevice, B->stream) != hipSuccess) throw std::string("upload of the work list failed");
+        by_precision(lead->precision, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(k_frozen_boxes_b<T>, dim3((g.nfb + 3) / 4, count), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, (int)g.off_frozen);
+            hipLaunchKernelGGL(k_energy_frozen_b<T>, dim3(g.nfb, count), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, (int)g.off_frozen);
+            hipLaunchKernelGGL(k_sum_frozen_b<T>, dim3((count + 63) / 64), dim3(64), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, count, (int)g.off_frozen, g.nfb, B->d_frozen_sum.p);
+        });
+        if (hipStreamSynchronize(B->stream) != hipSuccess) throw std::string("frozen-frozen energy launch failed");
+        sums.resize((size_t)2 * count);
+        if (hipMemcpy(sums.data(), B->d_frozen_sum.p, sizeof(double) * 2 * count, hipMemcpyDeviceToHost) != hipSuccess) throw std::string("download of the frozen-frozen energies failed");
+    } catch (std::string& e) { B->err = e; return false; }
+    for (int q = 0; q < count; q++) { BluesEngine* m = B->eng[lack[q]]; m->e_frozen[0] = sums[2 * q]; m->e_frozen[1] = sums[2 * q + 1]; m->e_frozen_valid = true; m->st_launches++; }
+    return true;
+}
+// Potential energies at the members' CURRENT alchemical parameters: when they can share them, the live members' energy launches in
+// lock step, one gather of their partials (and of their flags: one synchronisation for both), the sums on the host
+static bool prefetch_potential(BluesBatch* B, BluesEngine* lead, std::vector<char>& live) {
+    if (!prefetch_frozen(B, lead, live)) return false;
+    const int R = B->R(); int n_need = 0;
+    for (int r = 0; r < R; r++) if (live[r]) n_need += !B->eng[r]->ecache.find(B->eng[r]->cur_ls, B->eng[r]->cur_le, nullptr);
+    // members that already know their energy simply take part again (same launches, same value): masking them out of the
+    // shared launches would cost more than it saves, and ONE such member used to send all the others to their own evaluations
+    bool uniform = n_need > 1;
+    for (int r = 0; r < R && uniform; r++) if (live[r]) {
+        const BluesEngine* m = B->eng[r]; const char* why = "";
+        uniform = m->e_frozen_valid && m->cur_ls == lead->cur_ls && m->cur_le == lead->cur_le && m->lists_forced == lead->lists_forced && m->prog.n == 0 && batch_congruent_cached(B, r, lead, &why);
+    }
+    if (!uniform) return true;
+    if (batch_section_begin(B, lead)) return false;
+    bool ok = batch_each(B, true, [&](int r) { return live[r] != 0; }, [&](int r) { return energy_launch(B->eng[r]); }) < 0;
+    const EnergyShape g = energy_shape(lead);
+    const int n_nb = 2 * g.nw, n_b = g.nbb * T_NTYPES, n_al = lead->alch.empty() ? 0 : (lead->k2_nblocks_env + 1) * K2_NP, stride = n_nb + n_b + n_al + 2;
+    std::vector<double> slab; std::vector<int> hints;
+    try {
+        if (ok) {
+            if (B->d_gather.n != (size_t)R * stride) B->d_gather.alloc((size_t)R * stride);
+            by_precision(lead->precision, [&](auto tag) { using T = decltype(tag); hipLaunchKernelGGL(k_gather_energy_parts_b<T>, dim3(R), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_core.p, n_nb, n_b, n_al, stride, B->d_gather.p); });
+            batch_launch_hints(B);
+            ok = hipStreamSynchronize(B->stream) == hipSuccess;
+            if (ok) { B->d_gather.download(slab); batch_read_hints(B, hints); }
+        }
+    } catch (std::string& e) { B->err = e; ok = false; }
+    if (ok) for (int r = 0; r < R; r++) if (live[r] && !(hints[r] & 2)) {   // a member with an error flag keeps no cached value: its own call will report
+        BluesEngine* m = B->eng[r];
+        const double* o = slab.data() + (size_t)r * stride;
+        double T[BLUES_N_ENERGY_TERMS], one[2], E, E_one;
+        energy_sum(m, o, o + n_nb, (int)o[n_nb + n_b + n_al], o + n_nb + n_b, o[n_nb + n_b + n_al + 1], T, one);
+        energy_totals(m, T, one, &E, &E_one);
+        m->ecache.put(1.0, 1.0, E_one); m->ecache.put(m->cur_ls, m->cur_le, E);
+    }
+    B->st_prefetch_pe++;
+    return ok;
+}
+// kinetic energies (and the accumulators) of the live members.  Its way in is its own: the programs are flushed, without lock step, before the records are refreshed
+static bool prefetch_kinetic(BluesBatch* B, BluesEngine* lead, const std::vector<char>& live) {
+    const int R = B->R(); bool any = false;
+    for (int r = 0; r < R; r++) if (live[r]) any |= !B->eng[r]->ke_cache_valid;
+    if (!any) return true;
+    if (batch_enter(B)) return false;
+    bool ok = batch_each(B, false, [&](int r) { return live[r] != 0; }, [&](int r) { return flush_program(B->eng[r]); }) < 0;   // (nothing pending in the usual call sites)
+    B->leader = lead;
+    if (ok && batch_refresh_args(B)) ok = false;
+    std::vector<double> ke;
+    try {
+        if (ok) {
+            if (B->d_gather.n < (size_t)9 * R) B->d_gather.alloc((size_t)9 * R);
+            hipLaunchKernelGGL(k_kinetic_b, dim3(R), dim3(256), 0, B->stream, B->d_core.p, B->d_gather.p);
+            ok = hipStreamSynchronize(B->stream) == hipSuccess;
+            if (ok) { ke.resize((size_t)9 * R); ok = hipMemcpy(ke.data(), B->d_gather.p, sizeof(double) * 9 * R, hipMemcpyDeviceToHost) == hipSuccess; }
+        }
+    } catch (std::string& e) { B->err = e; ok = false; }
+    if (ok) for (int r = 0; r < R; r++) if (live[r]) {
+        BluesEngine* m = B->eng[r];
+        m->ke_cache = ke[r]; m->ke_cache_valid = true;
+        static_assert(sizeof(DevAccum) == 8 * sizeof(double), "k_kinetic_b copies eight doubles");
+        memcpy(&m->acc_cache, &ke[(size_t)R + 8 * r], sizeof(DevAccum)); m->acc_cache_valid = true; m->acc_cache_stamp = m->st_launches;
+    }
+    B->st_prefetch_ke++;
+    return ok;
+}
+
 // Total potential and/or kinetic energy of every active member with batched launches and ONE read-back; the values land in
 // the members' energy caches, where the per-member getState / setPositions bookkeeping that follows finds them (the
 // reference asks each Context separately: simulation.py:908-909).  Sums are formed on the host from the same partials in
@@ -2926,337 +3072,204 @@ static int batch_refresh_args(BluesBatch* B) {
 static int batch_prefetch(BluesBatch* B, int what) {
     const int R = B->R();
     if (R == 0) return 0;
-    std::vector<char> live(R), need(R, 0);
-    for (int r = 0; r < R; r++) if (B->active[r] && !B->failed[r] && resolve_xfer(B->eng[r])) B->failed[r] = 1;
-    {   // A few members whose State arrived far from where their tiles were laid out (a restore after a re-sort at a poll: resolve_xfer) have
-        // no layout now.  They are laid out HERE: left as they were, the check below sent ALL members to their own on-demand evaluation --
-        // 1024 lone energy evaluations, 0.15-0.25 s, in an iteration that names no layout event (round 6: three such iterations in 40 runs).
-        int lacking = 0, have = 0;
-        for (int r = 0; r < R; r++) if (B->active[r] && !B->failed[r] && B->eng[r]->have_positions && !B->eng[r]->straggler) { have++; lacking += !B->eng[r]->sorted_ok; }
-        if (lacking > 0 && lacking <= std::max(1, have / 8) && !B->lockstep) {
-            if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-            for (int r = 0; r < R; r++) if (B->active[r] && !B->failed[r] && B->eng[r]->have_positions && !B->eng[r]->straggler && !B->eng[r]->sorted_ok) {
-                if (ensure_sorted(B->eng[r])) B->failed[r] = 1;
-                B->st_relayouts++;
-            }
-        }
-    }
-    for (int r = 0; r < R; r++) live[r] = B->active[r] && !B->failed[r] && B->eng[r]->have_positions && B->eng[r]->sorted_ok && !B->eng[r]->straggler;   // (a straggler evaluates on demand, with launches of its own)
-    BluesEngine* lead = nullptr;
-    for (int r = 0; r < R; r++) if (live[r]) { lead = B->eng[r]; break; }
+    for (int r = 0; r < R; r++) if (member_in_call(B, r) && resolve_xfer(B->eng[r])) B->failed[r] = 1;
+    if (prefetch_lay_out(B)) return 1;
+    std::vector<char> live; BluesEngine* lead = prefetch_live(B, live);
     if (!lead) return 0;
-    for (int r = 0; r < R; r++) if (B->active[r] && !B->failed[r] && !live[r] && !B->eng[r]->straggler) return 0;   // a member without a layout yet: everybody evaluates on demand
+    for (int r = 0; r < R; r++) if (member_in_call(B, r) && !live[r] && !B->eng[r]->straggler) return 0;   // a member without a layout yet: everybody evaluates on demand
     const bool was_entered = B->entered;
-    bool ok = true;
-    auto pe_pass = [&]() -> int {   // potential energies at the members' CURRENT alchemical parameters
-        int n_need = 0, n_live = 0;
-        {   // the frozen-frozen constant of the members that have none.  One member (a chain that joined late): its own evaluation.
-            // Several -- every chain of a batch whose State came from the MD leg, in every iteration: the frozen atoms were given new
-            // positions -- in one launch over a work list; member by member this was a full lone energy evaluation with its host
-            // synchronisations each, 0.7 s per 1024 chains and iteration (half of the NCMC leg of a real run)
-            std::vector<int> lack;
-            for (int r = 0; r < R; r++) if (live[r] && !B->eng[r]->e_frozen_valid && !nocut(B->eng[r])) lack.push_back(r);
-            bool together = lack.size() > 1;
-            for (size_t q = 0; q < lack.size() && together; q++) { const char* why = ""; together = batch_congruent_cached(B, lack[q], lead, &why) && B->eng[lack[q]]->prog.n == 0; }
-            if (together) {
-                if (batch_enter(B)) return 1;
-                B->leader = lead;
-                if (batch_refresh_args(B)) { if (!was_entered) batch_leave(B); return 1; }
-                const EnergyShape g = energy_shape(lead);
-                const int count = (int)lack.size();
-                std::vector<double> sums;
-                try {
-                    if ((int)B->d_frozen_work.n < count) B->d_frozen_work.alloc(R);
-                    if ((int)B->d_frozen_sum.n < 2 * count) B->d_frozen_sum.alloc((size_t)2 * R);
-                    if (hipMemcpyAsync(B->d_frozen_work.p, lack.data(), sizeof(int) * count, hipMemcpyHostToDevice, B->stream) != hipSuccess) throw std::string("upload of the work list failed");
-                    if (lead->precision == 0) {
-                        hipLaunchKernelGGL(k_frozen_boxes_b<float>, dim3((g.nfb + 3) / 4, count), dim3(256), 0, B->stream, B->d_nb_f.p, B->d_frozen_work.p, (int)g.off_frozen);
-                        hipLaunchKernelGGL(k_energy_frozen_b<float>, dim3(g.nfb, count), dim3(256), 0, B->stream, B->d_nb_f.p, B->d_frozen_work.p, (int)g.off_frozen);
-                        hipLaunchKernelGGL(k_sum_frozen_b<float>, dim3((count + 63) / 64), dim3(64), 0, B->stream, B->d_nb_f.p, B->d_frozen_work.p, count, (int)g.off_frozen, g.nfb, B->d_frozen_sum.p);
-                    } else {
-                        hipLaunchKernelGGL(k_frozen_boxes_b<double>, dim3((g.nfb + 3) / 4, count), dim3(256), 0, B->stream, B->d_nb_d.p, B->d_frozen_work.p, (int)g.off_frozen);
-                        hipLaunchKernelGGL(k_energy_frozen_b<double>, dim3(g.nfb, count), dim3(256), 0, B->stream, B->d_nb_d.p, B->d_frozen_work.p, (int)g.off_frozen);
-                        hipLaunchKernelGGL(k_sum_frozen_b<double>, dim3((count + 63) / 64), dim3(64), 0, B->stream, B->d_nb_d.p, B->d_frozen_work.p, count, (int)g.off_frozen, g.nfb, B->d_frozen_sum.p);
-                    }
-                    if (hipStreamSynchronize(B->stream) != hipSuccess) throw std::string("frozen-frozen energy launch failed");
-                    sums.resize((size_t)2 * count);
-                    if (hipMemcpy(sums.data(), B->d_frozen_sum.p, sizeof(double) * 2 * count, hipMemcpyDeviceToHost) != hipSuccess) throw std::string("download of the frozen-frozen energies failed");
-                } catch (std::string& e) { B->err = e; if (!was_entered) batch_leave(B); return 1; }
-                for (int q = 0; q < count; q++) { BluesEngine* m = B->eng[lack[q]]; m->e_frozen[0] = sums[2 * q]; m->e_frozen[1] = sums[2 * q + 1]; m->e_frozen_valid = true; m->st_launches++; }
-            } else for (int r : lack) {
-                double E;
-                if (total_energy(B->eng[r], &E)) { B->failed[r] = 1; live[r] = 0; }
-            }
-        }
-        for (int r = 0; r < R; r++) if (live[r]) {
-            BluesEngine* m = B->eng[r];
-            n_live++;
-            need[r] = !m->ecache.find(m->cur_ls, m->cur_le, nullptr);
-            n_need += need[r];
-        }
-        // members that already know their energy simply take part again (same launches, same value): masking them out of the
-        // shared launches would cost more than it saves, and ONE such member used to send all the others to their own evaluations
-        bool uniform = n_need > 1;
-        for (int r = 0; r < R && uniform; r++) if (live[r]) {
-            const BluesEngine* m = B->eng[r];
-            uniform = m->e_frozen_valid && m->cur_ls == lead->cur_ls && m->cur_le == lead->cur_le && m->lists_forced == lead->lists_forced && m->prog.n == 0;
-            const char* why = "";
-            uniform = uniform && batch_congruent_cached(B, r, lead, &why);
-        }
-        if (uniform) {
-            if (batch_enter(B)) return 1;
-            B->leader = lead;
-            if (batch_refresh_args(B)) { if (!was_entered) batch_leave(B); return 1; }
-            B->lockstep = true;
-            for (int r = 0; r < R && ok; r++) if (live[r]) ok = energy_launch(B->eng[r]) == 0;
-            B->lockstep = false;
-            const EnergyShape g = energy_shape(lead);
-            const int n_nb = 2 * g.nw, n_b = g.nbb * T_NTYPES, n_al = lead->alch.empty() ? 0 : (lead->k2_nblocks_env + 1) * K2_NP, stride = n_nb + n_b + n_al + 2;
-            std::vector<double> slab; std::vector<int> hints;
-            try {
-                if (ok) {
-                    if (B->d_gather.n != (size_t)R * stride) B->d_gather.alloc((size_t)R * stride);
-                    if ((int)B->d_hints.n != R) B->d_hints.alloc(R);
-                    if (lead->precision == 0) hipLaunchKernelGGL(k_gather_energy_parts_b<float>, dim3(R), dim3(256), 0, B->stream, B->d_nb_f.p, B->d_core.p, n_nb, n_b, n_al, stride, B->d_gather.p);
-                    else hipLaunchKernelGGL(k_gather_energy_parts_b<double>, dim3(R), dim3(256), 0, B->stream, B->d_nb_d.p, B->d_core.p, n_nb, n_b, n_al, stride, B->d_gather.p);
-                    hipLaunchKernelGGL(k_gather_hints_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, B->d_core.p, R, B->d_hints.p);
-                    ok = hipStreamSynchronize(B->stream) == hipSuccess;
-                    if (ok) { B->d_gather.download(slab); B->d_hints.download(hints); }
-                }
-            } catch (std::string& e) { B->err = e; ok = false; }
-            if (ok) for (int r = 0; r < R; r++) if (live[r] && !(hints[r] & 2)) {   // a member with an error flag keeps no cached value: its own call will report
-                BluesEngine* m = B->eng[r];
-                const double* o = slab.data() + (size_t)r * stride;
-                double T[BLUES_N_ENERGY_TERMS], one[2], E, E_one;
-                energy_sum(m, o, o + n_nb, (int)o[n_nb + n_b + n_al], o + n_nb + n_b, o[n_nb + n_b + n_al + 1], T, one);
-                energy_totals(m, T, one, &E, &E_one);
-                m->ecache.put(1.0, 1.0, E_one); m->ecache.put(m->cur_ls, m->cur_le, E);
-            }
-            B->st_prefetch_pe++;
-        }
-        return 0;
-    };
-    if (what & 1) { if (pe_pass()) return 1; }
+    bool ok = !(what & 1) || prefetch_potential(B, lead, live);
     if (ok && (what & 4)) {   // ... and at lambda_sterics = lambda_electrostatics = 1 (what _computeAlchemicalCorrection asks next)
         std::vector<double> sv(2 * R);
         for (int r = 0; r < R; r++) { sv[2 * r] = B->eng[r]->cur_ls; sv[2 * r + 1] = B->eng[r]->cur_le; if (live[r]) { B->eng[r]->cur_ls = 1.0; B->eng[r]->cur_le = 1.0; } }
-        const int rc = pe_pass();
+        ok = prefetch_potential(B, lead, live);
         for (int r = 0; r < R; r++) { B->eng[r]->cur_ls = sv[2 * r]; B->eng[r]->cur_le = sv[2 * r + 1]; }
-        if (rc) return 1;
     }
-    if (ok && (what & 2)) {
-        bool any = false;
-        for (int r = 0; r < R; r++) if (live[r]) any |= !B->eng[r]->ke_cache_valid;
-        if (any) {
-            if (batch_enter(B)) return 1;
-            for (int r = 0; r < R && ok; r++) if (live[r]) ok = flush_program(B->eng[r]) == 0;   // (nothing pending in the usual call sites)
-            B->leader = lead;
-            if (ok && batch_refresh_args(B)) ok = false;
-            std::vector<double> ke;
-            try {
-                if (ok) {
-                    if (B->d_gather.n < (size_t)9 * R) B->d_gather.alloc((size_t)9 * R);
-                    hipLaunchKernelGGL(k_kinetic_b, dim3(R), dim3(256), 0, B->stream, B->d_core.p, B->d_gather.p);
-                    ok = hipStreamSynchronize(B->stream) == hipSuccess;
-                    if (ok) { ke.resize((size_t)9 * R); ok = hipMemcpy(ke.data(), B->d_gather.p, sizeof(double) * 9 * R, hipMemcpyDeviceToHost) == hipSuccess; }
-                }
-            } catch (std::string& e) { B->err = e; ok = false; }
-            if (ok) for (int r = 0; r < R; r++) if (live[r]) {
-                BluesEngine* m = B->eng[r];
-                m->ke_cache = ke[r]; m->ke_cache_valid = true;
-                static_assert(sizeof(DevAccum) == 8 * sizeof(double), "k_kinetic_b copies eight doubles");
-                memcpy(&m->acc_cache, &ke[(size_t)R + 8 * r], sizeof(DevAccum)); m->acc_cache_valid = true; m->acc_cache_stamp = m->st_launches;
-            }
-            B->st_prefetch_ke++;
-        }
-    }
-    if (!was_entered) batch_leave(B);
+    if (ok && (what & 2)) ok = prefetch_kinetic(B, lead, live);
+    if (!was_entered) batch_leave(B);   // (the one way out of whatever section the passes opened)
     if (!ok && B->err.empty()) B->err = "energy prefetch failed: " + lead->err;
     return ok ? 0 : 1;
+}
+enum { BATCH_DONE = -1 };   // ---- batch_do_steps, phase by phase.  A phase answers 0, 1 (an error of the batch itself: B->err) or BATCH_DONE: no member is left to step
+static inline void member_fail(BluesBatch* B, int* status, int r) { B->failed[r] = 1; status[r] = 1; }   // (was the lambda `fail`)
+// the leader issues the shared launches: the first member in the batch's layout (stragglers issue their own).  False: nobody is left
+// to step, neither a leader nor a straggler (was the lambdas `pick_leader` and `any_straggler`)
+static bool batch_pick_leader(BluesBatch* B) {
+    B->leader = nullptr;
+    for (int r = 0; r < B->R() && !B->leader; r++) if (member_shared(B, r)) B->leader = B->eng[r];
+    for (int r = 0; r < B->R() && !B->leader; r++) if (member_stepping(B, r) && B->eng[r]->straggler) return true;
+    return B->leader != nullptr;
+}
+static inline bool at_poll(const BluesEngine* h) { return h->h_step > 0 && h->h_step % RESORT_POLL == 0; }
+// call set-up (was the head of batch_do_steps): who steps, their layouts, the leader, stragglers back into the shared launches at
+// the start of a switch, congruence, the first refresh of the records
+static int batch_steps_begin(BluesBatch* B, bool tracing, int* status) {
+    const int R = B->R();
+    B->failed.assign(R, 0);   // failed[r] doubles as "skip this member": inactive members start out skipped (status stays 0)
+    for (int r = 0; r < R; r++) { status[r] = 0; B->eng[r]->tracing = tracing; if (!B->active[r]) B->failed[r] = 1; }
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && ensure_sorted(B->eng[r])) member_fail(B, status, r);
+    const bool somebody = batch_pick_leader(B);   // (the loop below runs with a leader only, and so cannot change this answer)
+    if (B->leader) for (int r = 0; r < R; r++) if (member_stepping(B, r) && B->eng[r]->straggler && B->eng[r]->h_step == 0 && B->eng[r]->have_positions) {
+        // a straggler at the start of a switch: back into the shared launches if its atoms fit the batch's shape again
+        if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
+        if (try_rejoin(B, B->eng[r], B->leader)) member_fail(B, status, r);
+    }
+    if (!somebody) return BATCH_DONE;
+    for (int r = 0; r < R; r++) if (member_shared(B, r)) { const char* why = ""; if (!batch_congruent_cached(B, r, B->leader, &why)) { B->err = std::string("replicas of a batch must be congruent; they differ in ") + why; return 1; } }
+    return batch_refresh_args(B);
+}
+// (was the lambda `split` of `phase`) the members in the shared launches whose control state differs from ref's go into odd;
+// returns how many agree with it
+static int lockstep_split(const BluesBatch* B, const BluesEngine* ref, std::vector<int>& odd) {
+    odd.clear();
+    const BatchSig lead = batch_sig(ref); int same = 0;
+    for (int r = 0; r < B->R(); r++) if (member_shared(B, r)) {
+        const BatchSig g = batch_sig(B->eng[r]);
+        if (!memcmp(&g, &lead, sizeof g)) { same++; continue; }
+        if (odd.empty() && B->tune.debug_lists) {
+#define SIGF(fld) if (g.fld != lead.fld) fprintf(stderr, "[lockstep] member %d differs from member %d in %s: %d against %d (step %d)\n", r, ref->batch_index, #fld, (int)g.fld, (int)lead.fld, g.h_step);
+            SIGF(h_step) SIGF(h_lambda_step) SIGF(h_prop) SIGF(h_first_step) SIGF(pass_L) SIGF(prog_n) SIGF(prog_trace) SIGF(nprop) SIGF(prog_draw_base) SIGF(noise_draw_base)
+            SIGF(pass_valid) SIGF(lists_forced) SIGF(vel_clean) SIGF(noise_valid) SIGF(tracing) SIGF(sorted_ok) SIGF(pass_valid_for_l) SIGF(have_positions) SIGF(fin_pending) SIGF(fin_mask)
+#undef SIGF
+        }
+        odd.push_back(r);
+    }
+    return same;
+}
+// (was the lambda `phase`) Runs f on every live member, in lock step when their signatures agree.  Round 6: a FEW members out of step with the rest
+// -- one that was laid out again inside this call (a re-sort at a poll, a straggler that came back: its lists are forced, its last
+// pass is gone) -- take the step on launches of their own, as a straggler does, and the others stay in lock step; one step later the
+// mirrors agree again.  (Until then ONE such member sent all of them through per-member launches for a step: 0.25 s per 1024 chains.)
+static int batch_phase(BluesBatch* B, int* status, int (*f)(BluesEngine*)) {
+    const int R = B->R();
+    if (!batch_pick_leader(B)) return 0;
+    if (B->leader) {
+        std::vector<int> odd;
+        int same = lockstep_split(B, B->leader, odd);
+        if ((int)odd.size() > same) { B->leader = B->eng[odd[0]]; same = lockstep_split(B, B->leader, odd); }   // (the first member is the one out of step: the majority leads)
+        if (odd.empty() || (int)odd.size() <= std::max(1, R / 32)) {
+            for (int r : odd) B->eng[r]->solo_now = true;   // (out of the shared records for this phase: batch_refresh_args)
+            const int rc = batch_refresh_args(B);
+            if (!rc) {
+                batch_each(B, true, [&](int r) { return member_in_lockstep(B, r); }, [&](int r) {
+                    if (!f(B->eng[r])) return 0;
+                    // a host-side failure of the leader leaves the shared launch sequence incomplete: every member is affected
+                    if (B->eng[r] == B->leader) { for (int q = 0; q < R; q++) if (member_in_lockstep(B, q)) { if (q != r) B->eng[q]->err = "batch leader failed: " + B->leader->err; member_fail(B, status, q); } }
+                    else member_fail(B, status, r);
+                    return 0;
+                });
+                B->st_lockstep_steps++;
+                if (!odd.empty()) B->st_partial_steps++;
+                for (int r : odd) if (member_stepping(B, r) && f(B->eng[r])) member_fail(B, status, r);
+            }
+            for (int r : odd) B->eng[r]->solo_now = false;
+            if (rc) return 1;
+        } else {
+            if (batch_refresh_args(B)) return 1;
+            for (int r = 0; r < R; r++) if (member_shared(B, r) && f(B->eng[r])) member_fail(B, status, r);
+            B->st_fallback_steps++;
+        }
+    } else if (batch_refresh_args(B)) return 1;   // leader change, a member dropped out, a re-sort: cheap no-op otherwise
+    // the stragglers: the same function, launches of their own (behind the shared ones, on the batch's stream)
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && B->eng[r]->straggler && f(B->eng[r])) member_fail(B, status, r);
+    return 0;
+}
+// the poll, after the hints are in: the members whose builders asked for a new order, re-sorted on the host's cores together (5-10 ms of host work each)
+static void batch_poll_resort(BluesBatch* B, int* status, const std::vector<int>& hints) {
+    std::vector<BluesEngine*> todo;
+    for (int r = 0; r < B->R(); r++) if (member_stepping(B, r) && at_poll(B->eng[r])) {
+        if (!resort_by_age(B->eng[r]) && !(hints[r] & 1)) continue;
+        // (a member that is due by age may have a hint pending as well: it is cleared -- and the lists given more room
+        // where they ask for it -- by resort_wanted, or the builder's request would cost a second re-sort 64 steps later)
+        const int want = resort_wanted(B->eng[r]);
+        if (want < 0) member_fail(B, status, r); else if (want) todo.push_back(B->eng[r]);
+    }
+    if (todo.empty()) return;
+    const auto t_rs = std::chrono::steady_clock::now();
+    relayout_many(todo, [](BluesEngine*) { return true; });
+    for (BluesEngine* m : todo) if (m->relayout_failed) member_fail(B, status, m->batch_index);
+    B->st_poll_resorts += (int64_t)todo.size();
+    B->st_resort_sec += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rs).count();
+}
+// ... and a member whose lists have outgrown the batch's layout shape steps on its own from here (make_straggler); a new
+// shape for everybody only when more than a handful have (rare: a run whose mobile atoms scatter for good)
+static int batch_poll_reshape(BluesBatch* B, int* status) {
+    bool over = false;
+    for (int r = 0; r < B->R(); r++) if (member_shared(B, r) && B->eng[r]->shape_overflow) {
+        if (batch_can_straggle(B, B->eng[r])) {
+            if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
+            if (make_straggler(B, B->eng[r])) member_fail(B, status, r);
+        } else over = true;
+    }
+    if (!over) return 0;
+    if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
+    if (batch_plan_shape(B, false)) return 1;
+    B->st_replans++;
+    return 0;
+}
+// The 64-step poll: same cadence as a lone engine (keyed on each member's own step counter, so results stay identical to solo runs);
+// one gathered read-back (batch_gather_hints) tells which members (if any) need the per-member treatment
+static int batch_poll(BluesBatch* B, int* status) {
+    bool due = false;
+    for (int r = 0; r < B->R(); r++) due |= member_stepping(B, r) && !nocut(B->eng[r]) && at_poll(B->eng[r]);
+    if (!due) return 0;
+    if (!batch_pick_leader(B)) return BATCH_DONE;
+    if (batch_phase(B, status, flush_program) || batch_refresh_args(B)) return 1;
+    std::vector<int> hints;
+    try { if (batch_gather_hints(B, hints)) { B->err = "stream synchronisation failed"; return 1; } } catch (std::string& e) { B->err = e; return 1; }
+    batch_poll_resort(B, status, hints);
+    return batch_poll_reshape(B, status);
+}
+// the work of an instantaneous Move needs U(x_moved) of every member that was edited: evaluate them together, and have add_work
+// leave the increments to batch_book_work
+static int batch_move_prefetch(BluesBatch* B) {
+    int edited = 0;
+    for (int r = 0; r < B->R(); r++) if (member_stepping(B, r)) { const BluesEngine* m = B->eng[r]; edited += m->h_step > 0 && m->h_step < m->nsteps && m->h_first_step >= 1 && m->x_edited && m->unpert_valid; }
+    if (edited > 1 && batch_prefetch(B, 1)) return 1;
+    B->defer_work = edited > 1; return 0;
+}
+// the members' deferred work increments in one launch (member by member it was a 1-thread launch each: 11 ms of host time for
+// 1024 chains at the head of the step after a Move, with the device idle)
+static int batch_book_work(BluesBatch* B) {
+    const int R = B->R(); int any = 0;
+    B->defer_work = false; B->h_wacc.assign(R, nullptr); B->h_wdelta.assign(R, 0.0);
+    for (int r = 0; r < R; r++) { BluesEngine* m = B->eng[r]; if (m->work_pending_set) { B->h_wacc[r] = m->d_acc.p; B->h_wdelta[r] = m->work_pending; any++; m->work_pending = 0.0; m->work_pending_set = false; } }
+    if (!any) return 0;
+    try { if ((int)B->d_wacc.n != R) { B->d_wacc.reserve(R); B->d_wdelta.reserve(R); } } catch (std::string& e) { B->err = e; return 1; }
+    if (hipMemcpyAsync(B->d_wacc.p, B->h_wacc.data(), sizeof(DevAccum*) * R, hipMemcpyHostToDevice, B->stream) != hipSuccess ||
+        hipMemcpyAsync(B->d_wdelta.p, B->h_wdelta.data(), sizeof(double) * R, hipMemcpyHostToDevice, B->stream) != hipSuccess) { B->err = "upload of the work increments failed"; return 1; }
+    hipLaunchKernelGGL(k_add_work_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, reinterpret_cast<DevAccum* const*>(B->d_wacc.p), B->d_wdelta.p, R);
+    if (hipGetLastError() != hipSuccess) { B->err = "k_add_work_b launch failed"; return 1; }
+    return 0;
+}
+// the tail of a stepping call: the energy ledger closed, the programs flushed, the error flags read
+static int batch_steps_end(BluesBatch* B, int* status) {
+    const int R = B->R();
+    bool pending = false;   // energy ledger: a measuring batch books the R stretch that is still pending, so that what the caller reads next is complete
+    for (int r = 0; r < R; r++) pending |= member_stepping(B, r) && ledger_on(B->eng[r]) && B->eng[r]->led_dirty;
+    if (pending && batch_phase(B, status, ledger_close)) return 1;
+    if (batch_phase(B, status, flush_program)) return 1;
+    for (int r = 0; r < R; r++) B->eng[r]->tracing = false;
+    // error flags: one gathered read-back tells which members (normally none) need their own check_flags; without it all of them do
+    bool gathered = false; std::vector<int> hints;
+    if (batch_pick_leader(B) && !batch_refresh_args(B)) try { gathered = !batch_gather_hints(B, hints) && (int)hints.size() == R; } catch (std::string&) { gathered = false; }
+    B->leader = B->eng[0];
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && (!gathered || (hints[r] & 2)) && check_flags(B->eng[r])) member_fail(B, status, r);
+    return 0;
 }
 
 // Advances every member by n_steps.  status[r] != 0: member r raised (message via blues_last_error(engine r)); the
 // others are unaffected.  Returns non-zero only for errors of the batch itself (B->err).
 static int batch_do_steps(BluesBatch* B, int n_steps, bool tracing, int* status) {
-    const int R = B->R();
-    // failed[r] doubles as "skip this member": inactive members start out skipped (status stays 0)
-    B->failed.assign(R, 0);
-    for (int r = 0; r < R; r++) { status[r] = 0; B->eng[r]->tracing = tracing; if (!B->active[r]) B->failed[r] = 1; }
-    auto fail = [&](int r) { B->failed[r] = 1; status[r] = 1; };
-    for (int r = 0; r < R; r++) if (!B->failed[r] && ensure_sorted(B->eng[r])) fail(r);
-    // the leader issues the shared launches: a member in the batch's layout (stragglers issue their own)
-    auto pick_leader = [&]() { B->leader = nullptr; for (int r = 0; r < R; r++) if (!B->failed[r] && !B->eng[r]->straggler) { B->leader = B->eng[r]; break; } };
-    auto any_straggler = [&]() { for (int r = 0; r < R; r++) if (!B->failed[r] && B->eng[r]->straggler) return true; return false; };
-    pick_leader();
-    if (B->leader) for (int r = 0; r < R; r++) if (!B->failed[r] && B->eng[r]->straggler && B->eng[r]->h_step == 0 && B->eng[r]->have_positions) {
-        // a straggler at the start of a switch: back into the shared launches if its atoms fit the batch's shape again
-        if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-        if (try_rejoin(B, B->eng[r], B->leader)) fail(r);
-    }
-    if (!B->leader && !any_straggler()) return 0;
-    for (int r = 0; r < R; r++) if (!B->failed[r] && !B->eng[r]->straggler) {
-        const char* why = "";
-        if (!batch_congruent_cached(B, r, B->leader, &why)) { B->err = std::string("replicas of a batch must be congruent; they differ in ") + why; return 1; }
-    }
-    if (batch_refresh_args(B)) return 1;
-    // phase(f): run f on every live member, in lock step when their signatures agree.  Round 6: a FEW members out of step with the rest
-    // -- one that was laid out again inside this call (a re-sort at a poll, a straggler that came back: its lists are forced, its last
-    // pass is gone) -- take the step on launches of their own, as a straggler does, and the others stay in lock step; one step later the
-    // mirrors agree again.  (Until then ONE such member sent all of them through per-member launches for a step: 0.25 s per 1024 chains.)
-    auto phase = [&](int (*f)(BluesEngine*)) -> int {
-        pick_leader();
-        if (!B->leader && !any_straggler()) return 0;
-        std::vector<int> odd;
-        if (B->leader) {
-            auto split = [&](const BluesEngine* ref) {
-                odd.clear();
-                const BatchSig lead = batch_sig(ref);
-                int same = 0;
-                for (int r = 0; r < R; r++) if (!B->failed[r] && !B->eng[r]->straggler) {
-                    const BatchSig g = batch_sig(B->eng[r]);
-                    if (!memcmp(&g, &lead, sizeof g)) { same++; continue; }
-                    if (odd.empty() && B->tune.debug_lists) {
-#define SIGF(fld) if (g.fld != lead.fld) fprintf(stderr, "[lockstep] member %d differs from member %d in %s: %d against %d (step %d)\n", r, ref->batch_index, #fld, (int)g.fld, (int)lead.fld, g.h_step);
-                        SIGF(h_step) SIGF(h_lambda_step) SIGF(h_prop) SIGF(h_first_step) SIGF(pass_L) SIGF(prog_n) SIGF(prog_trace) SIGF(nprop) SIGF(prog_draw_base) SIGF(noise_draw_base)
-                        SIGF(pass_valid) SIGF(lists_forced) SIGF(vel_clean) SIGF(noise_valid) SIGF(tracing) SIGF(sorted_ok) SIGF(pass_valid_for_l) SIGF(have_positions) SIGF(fin_pending) SIGF(fin_mask)
-#undef SIGF
-                    }
-                    odd.push_back(r);
-                }
-                return same;
-            };
-            int same = split(B->leader);
-            if ((int)odd.size() > same) { B->leader = B->eng[odd[0]]; same = split(B->leader); }   // (the first member is the one out of step: the majority leads)
-            const bool partial = !odd.empty() && (int)odd.size() <= std::max(1, R / 32);
-            if (odd.empty() || partial) {
-                for (int r : odd) B->eng[r]->solo_now = true;   // (out of the shared records for this phase: batch_refresh_args)
-                int rc = batch_refresh_args(B);
-                if (!rc) {
-                    B->lockstep = true;
-                    for (int r = 0; r < R; r++) if (!B->failed[r] && !B->eng[r]->straggler && !B->eng[r]->solo_now && f(B->eng[r])) {
-                        // a host-side failure of the leader leaves the shared launch sequence incomplete: every member is affected
-                        if (B->eng[r] == B->leader) { for (int q = 0; q < R; q++) if (!B->failed[q] && !B->eng[q]->straggler && !B->eng[q]->solo_now) { if (q != r) B->eng[q]->err = "batch leader failed: " + B->leader->err; fail(q); } }
-                        else fail(r);
-                    }
-                    B->lockstep = false;
-                    B->st_lockstep_steps++;
-                    if (partial) B->st_partial_steps++;
-                    for (int r : odd) if (!B->failed[r] && f(B->eng[r])) fail(r);
-                }
-                for (int r : odd) B->eng[r]->solo_now = false;
-                if (rc) return 1;
-            } else {
-                if (batch_refresh_args(B)) return 1;
-                for (int r = 0; r < R; r++) if (!B->failed[r] && !B->eng[r]->straggler && f(B->eng[r])) fail(r);
-                B->st_fallback_steps++;
-            }
-        } else if (batch_refresh_args(B)) return 1;   // leader change, a member dropped out, a re-sort: cheap no-op otherwise
-        // the stragglers: the same function, launches of their own (behind the shared ones, on the batch's stream)
-        for (int r = 0; r < R; r++) if (!B->failed[r] && B->eng[r]->straggler && f(B->eng[r])) fail(r);
-        return 0;
-    };
+    if (const int rc = batch_steps_begin(B, tracing, status)) return rc == BATCH_DONE ? 0 : rc;
     for (int s = 0; s < n_steps; s++) {
-        // same cadence as a lone engine (keyed on each member's own step counter, so results stay identical to solo runs);
-        // one gathered read-back tells which members (if any) need the per-member treatment
-        {
-            bool due = false;
-            for (int r = 0; r < R; r++) due |= !B->failed[r] && !nocut(B->eng[r]) && B->eng[r]->h_step > 0 && B->eng[r]->h_step % RESORT_POLL == 0;
-            if (due) {
-                pick_leader();
-                if (!B->leader && !any_straggler()) return 0;
-                if (phase(flush_program)) return 1;
-                if (batch_refresh_args(B)) return 1;
-                std::vector<int> hints;
-                try {
-                    if ((int)B->d_hints.n != R) B->d_hints.alloc(R);
-                    hipLaunchKernelGGL(k_gather_hints_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, B->d_core.p, R, B->d_hints.p);
-                    if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-                    B->d_hints.download(hints);
-                } catch (std::string& e) { B->err = e; return 1; }
-                {   // the members whose builders asked for a new order: re-sorted on the host's cores together (5-10 ms of host work each)
-                    std::vector<BluesEngine*> todo;
-                    for (int r = 0; r < R; r++)
-                        if (!B->failed[r] && B->eng[r]->h_step > 0 && B->eng[r]->h_step % RESORT_POLL == 0) {
-                            const bool aged = resort_by_age(B->eng[r]);
-                            if (!aged && !(hints[r] & 1)) continue;
-                            // (a member that is due by age may have a hint pending as well: it is cleared -- and the lists given more room
-                            // where they ask for it -- here, or the builder's request would cost a second re-sort 64 steps later)
-                            const int due = poll_resort_due(B->eng[r]);
-                            if (due < 0) { fail(r); continue; }
-                            if (aged && !due) B->eng[r]->st_resorts++;
-                            if (aged || due) todo.push_back(B->eng[r]);
-                        }
-                    if (!todo.empty()) {
-                        const auto t_rs = std::chrono::steady_clock::now();
-                        relayout_many(todo, [](BluesEngine*) { return true; });
-                        for (BluesEngine* m : todo) if (m->relayout_failed) fail(m->batch_index);
-                        B->st_poll_resorts += (int64_t)todo.size();
-                        B->st_resort_sec += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_rs).count();
-                    }
-                }
-                {   // a member whose lists have outgrown the batch's layout shape: it steps on its own from here (make_straggler); a new
-                    // shape for everybody only when more than a handful have (rare: a run whose mobile atoms scatter for good)
-                    bool over = false;
-                    for (int r = 0; r < R; r++) if (!B->failed[r] && B->eng[r]->shape_overflow && !B->eng[r]->straggler) {
-                        if (batch_can_straggle(B, B->eng[r])) {
-                            if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-                            if (make_straggler(B, B->eng[r])) fail(r);
-                        } else over = true;
-                    }
-                    if (over) {
-                        if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-                        if (batch_plan_shape(B, false)) return 1;
-                        B->st_replans++;
-                    }
-                }
-            }
-        }
-        {   // the work of an instantaneous Move needs U(x_moved) of every member that was edited: evaluate them together
-            int edited = 0;
-            for (int r = 0; r < R; r++) if (!B->failed[r]) { const BluesEngine* m = B->eng[r]; edited += m->h_step > 0 && m->h_step < m->nsteps && m->h_first_step >= 1 && m->x_edited && m->unpert_valid; }
-            if (edited > 1 && batch_prefetch(B, 1)) return 1;
-            B->defer_work = edited > 1;
-        }
-        for (int r = 0; r < R; r++) if (!B->failed[r] && step_head(B->eng[r])) fail(r);
-        if (B->defer_work) {
-            // the members' work increments in one launch (member by member it was a 1-thread launch each: 11 ms of host time for
-            // 1024 chains at the head of the step after a Move, with the device idle)
-            B->defer_work = false;
-            B->h_wacc.assign(R, nullptr); B->h_wdelta.assign(R, 0.0);
-            int any = 0;
-            for (int r = 0; r < R; r++) { BluesEngine* m = B->eng[r]; if (m->work_pending_set) { B->h_wacc[r] = m->d_acc.p; B->h_wdelta[r] = m->work_pending; any++; m->work_pending = 0.0; m->work_pending_set = false; } }
-            if (any) {
-                try { if ((int)B->d_wacc.n != R) { B->d_wacc.reserve(R); B->d_wdelta.reserve(R); } } catch (std::string& e) { B->err = e; return 1; }
-                hipStream_t st = B->stream;
-                if (hipMemcpyAsync(B->d_wacc.p, B->h_wacc.data(), sizeof(DevAccum*) * R, hipMemcpyHostToDevice, st) != hipSuccess ||
-                    hipMemcpyAsync(B->d_wdelta.p, B->h_wdelta.data(), sizeof(double) * R, hipMemcpyHostToDevice, st) != hipSuccess) { B->err = "upload of the work increments failed"; return 1; }
-                hipLaunchKernelGGL(k_add_work_b, dim3((R + 255) / 256), dim3(256), 0, st, reinterpret_cast<DevAccum* const*>(B->d_wacc.p), B->d_wdelta.p, R);
-                if (hipGetLastError() != hipSuccess) { B->err = "k_add_work_b launch failed"; return 1; }
-            }
-        }
-        if (phase(step_body)) return 1;
+        if (const int rc = batch_poll(B, status)) return rc == BATCH_DONE ? 0 : rc;
+        if (batch_move_prefetch(B)) return 1;
+        for (int r = 0; r < B->R(); r++) if (member_stepping(B, r) && step_head(B->eng[r])) member_fail(B, status, r);
+        if (B->defer_work && batch_book_work(B)) return 1;
+        if (batch_phase(B, status, step_body)) return 1;
     }
-    {   // energy ledger: a measuring batch books the R stretch that is still pending, so that what the caller reads next is complete
-        bool pending = false;
-        for (int r = 0; r < R; r++) pending |= !B->failed[r] && ledger_on(B->eng[r]) && B->eng[r]->led_dirty;
-        if (pending && phase(ledger_close)) return 1;
-    }
-    if (phase(flush_program)) return 1;
-    for (int r = 0; r < R; r++) B->eng[r]->tracing = false;
-    // error flags: one gathered read-back tells which members (normally none) need their own check_flags
-    pick_leader();
-    bool gathered = false;
-    std::vector<int> hints;
-    if ((B->leader || any_straggler()) && !batch_refresh_args(B)) {
-        try {
-            if ((int)B->d_hints.n != R) B->d_hints.alloc(R);
-            hipLaunchKernelGGL(k_gather_hints_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, B->d_core.p, R, B->d_hints.p);
-            if (hipStreamSynchronize(B->stream) == hipSuccess) { B->d_hints.download(hints); gathered = (int)hints.size() == R; }
-        } catch (std::string&) { gathered = false; }
-    }
-    B->leader = B->eng[0];
-    for (int r = 0; r < R; r++) if (!B->failed[r] && (!gathered || (hints[r] & 2)) && check_flags(B->eng[r])) fail(r);
-    return 0;
+    return batch_steps_end(B, status);
 }
 
 // ------------------------------------------------------------------ C-ABI
@@ -4174,6 +4187,7 @@ int blues_batch_mesh_energy(BluesBatch* B, int32_t with_alchemical_charges, cons
     for (int r = 0; r < R; r++) out[r] = 0.0;
     BluesEngine* lead = nullptr;
     B->failed.assign(R, 0);
+    auto unmask = [&]() { for (int q = 0; q < R; q++) B->active[q] = 1; };   // (the caller's mask is not kept, and not every exit comes by here: ADVICE.md)
     std::vector<int> alone;   // (stragglers: their own launches)
     for (int r = 0; r < R; r++) {
         B->active[r] = mask ? (mask[r] != 0) : 1;
@@ -4184,32 +4198,25 @@ int blues_batch_mesh_energy(BluesBatch* B, int32_t with_alchemical_charges, cons
         if (m->straggler) { alone.push_back(r); B->active[r] = 0; continue; }
         if (!lead) lead = m;
     }
-    for (int r : alone) if (blues_mesh_energy(B->eng[r], with_alchemical_charges, &out[r])) { B->err = "mesh energy: " + B->eng[r]->err; for (int q = 0; q < R; q++) B->active[q] = 1; return 1; }
-    if (!lead || !lead->pme) { for (int q = 0; q < R; q++) B->active[q] = 1; return 0; }
-    for (int r = 0; r < R; r++) if (B->active[r]) { const char* why = ""; if (!batch_congruent_cached(B, r, lead, &why)) { B->err = std::string("mesh energy: members differ in ") + why; return 1; } }
+    for (int r : alone) if (blues_mesh_energy(B->eng[r], with_alchemical_charges, &out[r])) { B->err = "mesh energy: " + B->eng[r]->err; unmask(); return 1; }
+    if (!lead || !lead->pme) { unmask(); return 0; }
+    for (int r = 0; r < R; r++) if (member_in_call(B, r)) { const char* why = ""; if (!batch_congruent_cached(B, r, lead, &why)) { B->err = std::string("mesh energy: members differ in ") + why; return 1; } }
     const bool was_entered = B->entered;
-    if (batch_enter(B)) return 1;
-    B->leader = lead;
-    int rc = batch_refresh_args(B);
-    if (!rc) {
-        B->lockstep = true;
-        for (int r = 0; r < R && !rc; r++) if (B->active[r]) rc = launch_pme(B->eng[r], 1 | (with_alchemical_charges ? 2 : 0));
-        B->lockstep = false;
-        if (rc) B->err = "mesh energy: " + lead->err;
-    }
+    int rc = batch_section_begin(B, lead);
+    if (rc && !B->entered) return 1;   // (batch_enter failed)
+    if (!rc && batch_each(B, true, [&](int r) { return member_in_call(B, r); }, [&](int r) { return launch_pme(B->eng[r], 1 | (with_alchemical_charges ? 2 : 0)); }) >= 0) { B->err = "mesh energy: " + lead->err; rc = 1; }
     if (!rc) {
         try {
             if (B->d_gather.n < (size_t)R) B->d_gather.alloc((size_t)R);
-            if (lead->precision == 0) hipLaunchKernelGGL(k_gather_pme_e_b<float>, dim3((R + 255) / 256), dim3(256), 0, B->stream, B->d_nb_f.p, R, B->d_gather.p);
-            else hipLaunchKernelGGL(k_gather_pme_e_b<double>, dim3((R + 255) / 256), dim3(256), 0, B->stream, B->d_nb_d.p, R, B->d_gather.p);
+            by_precision(lead->precision, [&](auto tag) { using T = decltype(tag); hipLaunchKernelGGL(k_gather_pme_e_b<T>, dim3((R + 255) / 256), dim3(256), 0, B->stream, batch_reps_nb<T>(B), R, B->d_gather.p); });
             std::vector<double> got(R, 0.0);
             if (hipStreamSynchronize(B->stream) != hipSuccess || hipMemcpy(got.data(), B->d_gather.p, sizeof(double) * R, hipMemcpyDeviceToHost) != hipSuccess) { B->err = "mesh energy: read-back failed"; rc = 1; }
-            else for (int r = 0; r < R; r++) if (B->active[r]) out[r] = got[r];
+            else for (int r = 0; r < R; r++) if (member_in_call(B, r)) out[r] = got[r];
         } catch (std::string& e) { B->err = e; rc = 1; }
     }
     if (!was_entered) batch_leave(B);
     B->leader = B->eng[0];
-    for (int r = 0; r < R; r++) B->active[r] = 1;
+    unmask();
     return rc;
 }
 
@@ -4524,14 +4531,19 @@ static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 static int batch_max_n(const BluesBatch* B) { int m = 0; for (const BluesEngine* h : B->eng) m = std::max(m, h->n); return m; }
 static int batch_min_n(const BluesBatch* B) { int m = B->eng[0]->n; for (const BluesEngine* h : B->eng) m = std::min(m, h->n); return m; }
 
+// how a batched boundary call opens: the device, an arena of `bytes`, the pending programs of the members in the mask (null: all;
+// flush false: none, the call reads no live state) flushed, the members on the batch's stream.  The caller leaves (batch_leave).
+static int batch_call_begin(BluesBatch* B, size_t bytes, const int32_t* mask, bool flush = true) {
+    if (hipSetDevice(B->eng[0]->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
+    if (batch_arena(B, bytes)) return 1;
+    for (int r = 0; r < B->R() && flush; r++) if ((!mask || mask[r]) && flush_program(B->eng[r])) { B->err = B->eng[r]->err; return 1; }
+    return batch_enter(B);
+}
+
 int blues_batch_snapshot_capture(BluesBatch* B, int32_t what, const int32_t* mask, BluesSnapshot** out) {
     if (!B || !out || !(what & 3)) return 2;
     const int R = B->R();
-    BluesEngine* h0 = B->eng[0];
-    if (hipSetDevice(h0->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
-    if (batch_arena(B, sizeof(Copy6Args) * R)) return 1;
-    for (int r = 0; r < R; r++) if ((!mask || mask[r]) && flush_program(B->eng[r])) { B->err = B->eng[r]->err; return 1; }
-    if (batch_enter(B)) return 1;
+    if (batch_call_begin(B, sizeof(Copy6Args) * R, mask)) return 1;
     Copy6Args* args = reinterpret_cast<Copy6Args*>(B->h_arena);
     for (int r = 0; r < R; r++) {
         BluesEngine* h = B->eng[r];
@@ -4645,13 +4657,9 @@ int blues_batch_restore_edited(BluesBatch* B, BluesSnapshot* const* snaps, const
 int blues_batch_read_atoms(BluesBatch* B, BluesSnapshot* const* snaps, int32_t what, const int32_t* idx, int32_t n_idx, double* out) {
     if (!B || !idx || !out || n_idx <= 0 || (what != 1 && what != 2)) return 2;
     const int R = B->R();
-    BluesEngine* h0 = B->eng[0];
-    if (hipSetDevice(h0->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
     { const int nmin = batch_min_n(B); for (int e = 0; e < n_idx; e++) if (idx[e] < 0 || idx[e] >= nmin) { B->err = "atom out of range"; return 1; } }
     const size_t off_src = 0, off_idx = align16(sizeof(double*) * 3 * R), off_out = align16(off_idx + sizeof(int) * n_idx), total = off_out + sizeof(double) * 3 * (size_t)n_idx * R;
-    if (batch_arena(B, total)) return 1;
-    for (int r = 0; r < R; r++) if (!snaps && flush_program(B->eng[r])) { B->err = B->eng[r]->err; return 1; }
-    if (batch_enter(B)) return 1;
+    if (batch_call_begin(B, total, nullptr, !snaps)) return 1;   // (it flushes only when it reads live state)
     const double** src = reinterpret_cast<const double**>(B->h_arena + off_src);
     for (int r = 0; r < R; r++) for (int k = 0; k < 3; k++) {
         const double* p = nullptr;
@@ -4676,10 +4684,7 @@ int blues_batch_read_atoms(BluesBatch* B, BluesSnapshot* const* snaps, int32_t w
 int blues_batch_reset(BluesBatch* B, const int32_t* mask) {
     if (!B) return 2;
     const int R = B->R();
-    if (hipSetDevice(B->eng[0]->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
-    if (batch_arena(B, sizeof(DevAccum*) * R)) return 1;
-    for (int r = 0; r < R; r++) if ((!mask || mask[r]) && flush_program(B->eng[r])) { B->err = B->eng[r]->err; return 1; }
-    if (batch_enter(B)) return 1;
+    if (batch_call_begin(B, sizeof(DevAccum*) * R, mask)) return 1;
     DevAccum** acc = reinterpret_cast<DevAccum**>(B->h_arena);
     for (int r = 0; r < R; r++) {
         BluesEngine* h = B->eng[r];
@@ -4700,11 +4705,7 @@ int blues_batch_reset(BluesBatch* B, const int32_t* mask) {
 int blues_batch_set_velocities_to_temperature(BluesBatch* B, double temperature, const uint64_t* seeds, const int32_t* mask) {
     if (!B || !seeds) return 2;
     const int R = B->R();
-    BluesEngine* h0 = B->eng[0];
-    if (hipSetDevice(h0->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
-    if (batch_arena(B, sizeof(MaxwellArgs) * R)) return 1;
-    for (int r = 0; r < R; r++) if ((!mask || mask[r]) && flush_program(B->eng[r])) { B->err = B->eng[r]->err; return 1; }
-    if (batch_enter(B)) return 1;
+    if (batch_call_begin(B, sizeof(MaxwellArgs) * R, mask)) return 1;
     MaxwellArgs* ma = reinterpret_cast<MaxwellArgs*>(B->h_arena);
     for (int r = 0; r < R; r++) {
         BluesEngine* h = B->eng[r];
@@ -4721,18 +4722,15 @@ int blues_batch_set_velocities_to_temperature(BluesBatch* B, double temperature,
     B->failed.assign(R, 0);
     for (int r = 0; r < R; r++) { B->active[r] = (!mask || mask[r]) ? 1 : 0; if (!B->active[r]) B->failed[r] = 1; }
     BluesEngine* lead = nullptr;
-    for (int r = 0; r < R && !rc; r++) if (!B->failed[r]) { if (!lead) lead = B->eng[r]; if (ensure_sorted(B->eng[r]) || emit(B->eng[r], OP_RATTLE)) { B->err = B->eng[r]->err; rc = 1; } }
+    for (int r = 0; r < R && !rc; r++) if (member_stepping(B, r)) { if (!lead) lead = B->eng[r]; if (ensure_sorted(B->eng[r]) || emit(B->eng[r], OP_RATTLE)) { B->err = B->eng[r]->err; rc = 1; } }
     if (!rc && lead) {
         B->leader = lead;
         bool uniform = true;
         const BatchSig ls = batch_sig(lead);
-        for (int r = 0; r < R && uniform; r++) if (!B->failed[r]) { const BatchSig g = batch_sig(B->eng[r]); const char* why = ""; uniform = !memcmp(&g, &ls, sizeof g) && batch_congruent_cached(B, r, lead, &why); }
+        for (int r = 0; r < R && uniform; r++) if (member_stepping(B, r)) { const BatchSig g = batch_sig(B->eng[r]); const char* why = ""; uniform = !memcmp(&g, &ls, sizeof g) && batch_congruent_cached(B, r, lead, &why); }
         if (uniform && batch_refresh_args(B)) rc = 1;
-        if (!rc) {
-            B->lockstep = uniform;
-            for (int r = 0; r < R && !rc; r++) if (!B->failed[r] && flush_program(B->eng[r])) { B->err = B->eng[r]->err; rc = 1; }
-            B->lockstep = false;
-        }
+        const int bad = rc ? -1 : batch_each(B, uniform, [&](int r) { return member_stepping(B, r); }, [&](int r) { return flush_program(B->eng[r]); });
+        if (bad >= 0) { B->err = B->eng[bad]->err; rc = 1; }
     }
     B->active = saved_active; B->leader = B->eng[0];
     batch_leave(B);

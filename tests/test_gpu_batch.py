@@ -194,6 +194,67 @@ def test_batch_with_frozen_atoms_and_moves(Engine, tol_box, same_decomposition):
     B.close()
 
 
+# The integer fields of B.stats() and B.counters() after the call sequence of the test below, per same_decomposition value.  Taken from
+# one run of this test against the library of the commit before the batch's host loop was split into named phases (both dictionaries
+# of that run are in profiles/batch_host_loop/README.md): the split must leave every one of them as it was.
+_HOST_LOOP_STATS = {
+    "0": {"lockstep_steps": 75, "fallback_steps": 0, "replicas": 5, "batched_energy_evaluations": 0},
+    "1": {"lockstep_steps": 75, "fallback_steps": 0, "replicas": 5, "batched_energy_evaluations": 0},
+}
+_HOST_LOOP_COUNTERS = {
+    "0": {"replans": 0, "relayouts": 5, "poll_resorts": 0, "reshapes": 0, "resorts": 0, "tiles_per_list": 1, "jcap": 1024, "nonbonded_kernel": 3,
+          "stragglers": 0, "straggled": 0, "rejoined": 0, "partial_steps": 0},
+    "1": {"replans": 0, "relayouts": 5, "poll_resorts": 4, "reshapes": 0, "resorts": 4, "tiles_per_list": 1, "jcap": 1024, "nonbonded_kernel": 0,
+          "stragglers": 0, "straggled": 0, "rejoined": 0, "partial_steps": 0},
+}
+
+
+def test_a_masked_batch_with_moves_across_a_poll_equals_the_lone_chains(Engine, tol_box, same_decomposition):
+    """One call sequence through the parts of the batch's host loop that the shorter tests leave out: a member masked out of every
+    call, a Move of several members (the batched energy prefetch and the one launch that books their work) and the 64-step poll."""
+    from blues_amd.engine import NativeBatch
+    s, v = tol_box
+    lig = np.arange(15)
+    near = systems.nearest_molecules(s, lig, 120, exclude_idx=lig)
+    sf = systems.freeze_except(s, np.concatenate([lig, near]))
+    vf = v * (sf.mass[:, None] > 0)
+    R, n, masked, moved = 5, 80, 3, (0, 1, 4)
+    vels = _replica_inputs(sf, vf, R)
+    rot = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+
+    def edit(g):
+        x = g.get_positions(); c = x[lig].mean(0); x[lig] = (x[lig] - c) @ rot.T + c; g.set_positions(x)
+
+    def run(engs, stepper):
+        stepper(40)
+        for r in moved:
+            edit(engs[r])
+        stepper(32)          # every stepping member passes step 64: the poll
+
+    solo = _make(Engine, sf, vels, n, 0)
+    run(solo, lambda k: [g.step(k) for r, g in enumerate(solo) if r != masked])
+    bat = _make(Engine, sf, vels, n, 0)
+    B = NativeBatch(bat)
+    active = [r != masked for r in range(R)]
+    x3_before = bat[masked].get_positions()
+    run(bat, lambda k: B.step(k, active=active))
+    for r in range(R):
+        if r == masked:
+            continue
+        xs, vs, w_s = _state(solo[r]); xb, vb, w_b = _state(bat[r])
+        assert bat[r].get_global("step") == 72
+        assert np.array_equal(xs, xb) and np.array_equal(vs, vb) and w_s == w_b, r
+    assert np.array_equal(bat[masked].get_positions(), x3_before) and bat[masked].get_global("step") == 0
+    st = B.stats()
+    ct = {k: c for k, c in B.counters().items() if not k.endswith("_seconds")}
+    print("host loop, same_decomposition=%s: stats %r counters %r" % (same_decomposition, st, ct))
+    assert st == _HOST_LOOP_STATS[same_decomposition]
+    assert ct == _HOST_LOOP_COUNTERS[same_decomposition]
+    B.close()
+    for g in solo + bat:
+        g.close()
+
+
 def test_batch_other_programs_and_inactive_members(Engine, tol_box, same_decomposition):
     """General op interpreter (another splitting, nprop > 1) through the batch; a member masked out is left untouched."""
     from blues_amd.engine import NativeBatch
