@@ -16,6 +16,10 @@ NB_PME_DIRECT = 1
 NB_PME = 2
 PAIR_STANDARD, PAIR_ETHYLENE = 0, 1      # BluesSystemDesc.custom_pair_mode
 MAX_CENTROID_BONDS, MAX_CENTROID_GROUP = 4, 8
+GB_NONE, GB_OBC1, GB_OBC2 = 0, 1, 2        # BluesImplicitSolventDesc.model
+GB_MODELS = {"OBC1": GB_OBC1, "OBC2": GB_OBC2}
+GB_RADIUS_OFFSET = 0.009                   # nm (OpenMM's GBSAOBCForce dielectric offset)
+GB_SURFACE_AREA_ENERGY = 2.25936           # kJ/mol/nm^2 (OpenMM's default)
 N_ENERGY_TERMS = 10
 N_STATS = 22
 N_BATCH_COUNTERS = 15
@@ -64,6 +68,15 @@ class BluesIntegratorDesc(C.Structure):
     ]
 
 
+class BluesImplicitSolventDesc(C.Structure):
+    _fields_ = [
+        ("model", C.c_int32),
+        ("solute_dielectric", C.c_double), ("solvent_dielectric", C.c_double),
+        ("surface_area_energy", C.c_double),
+        ("radius", _dp), ("scale", _dp),
+    ]
+
+
 class BluesTuning(C.Structure):
     """include/blues_engine.h: BluesTuning (launch-policy overrides; the library reads no environment variables)."""
     _fields_ = [
@@ -91,6 +104,31 @@ def _i32(a, shape=None):
     if shape is not None:
         a = a.reshape(shape)
     return a
+
+
+@dataclass
+class ImplicitSolventData:
+    """GB-OBC implicit solvent of a NoCutoff System (BluesImplicitSolventDesc in include/blues_engine.h)."""
+    model: int                           # GB_OBC1 / GB_OBC2
+    radius: np.ndarray                   # [n] nm (prmtop RADII)
+    scale: np.ndarray                    # [n] (prmtop SCREEN)
+    solute_dielectric: float = 1.0
+    solvent_dielectric: float = 78.5
+    surface_area_energy: float = GB_SURFACE_AREA_ENERGY   # 0 switches the ACE surface term off
+
+    def subset(self, index):
+        """The same model over a selection (or repetition) of the atoms."""
+        return ImplicitSolventData(self.model, np.asarray(self.radius, dtype=np.float64)[index].copy(), np.asarray(self.scale, dtype=np.float64)[index].copy(),
+                                   self.solute_dielectric, self.solvent_dielectric, self.surface_area_energy)
+
+    def to_desc(self):
+        keep = {"radius": _f64(self.radius, (-1,)), "scale": _f64(self.scale, (-1,))}
+        d = BluesImplicitSolventDesc()
+        d.model = int(self.model)
+        d.solute_dielectric = float(self.solute_dielectric); d.solvent_dielectric = float(self.solvent_dielectric)
+        d.surface_area_energy = float(self.surface_area_energy)
+        d.radius = keep["radius"].ctypes.data_as(_dp); d.scale = keep["scale"].ctypes.data_as(_dp)
+        return d, keep
 
 
 @dataclass
@@ -136,6 +174,7 @@ class SystemData:
     extras: dict = None                  # oracle-only test extras (custom forces of the ethylene known-answer system); refused by the engine, which takes them from the two typed fields below
     custom_pair_mode: int = PAIR_STANDARD  # NB_NOCUTOFF only; PAIR_ETHYLENE: q/r^2 + lambda-scaled 12-6 between alchemical and non-alchemical atoms
     centroid_bonds: tuple = ()           # NB_NOCUTOFF only; entries (idx1, w1, idx2, w2, k): E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w)
+    implicit_solvent: ImplicitSolventData = None   # NB_NOCUTOFF only; GB-OBC with the ACE surface term (blues_engine_create_gb)
 
     @property
     def n_atoms(self):
@@ -165,6 +204,38 @@ class SystemData:
                     raise ValueError("centroid bond %d: atom index out of range" % b)
                 if not np.all(np.isfinite(w)) or w.sum() == 0.0:
                     raise ValueError("centroid bond %d: the weights of a group sum to zero (or are not finite)" % b)
+
+    def check_implicit_solvent(self, integrator=None):
+        """What blues_engine_create_gb refuses about implicit solvent (with `integrator`, an IntegratorData: about the pair), raised
+        before a library is loaded (ValueError)."""
+        gb = self.implicit_solvent
+        if gb is None or int(gb.model) == GB_NONE:
+            return
+        if integrator is not None and (integrator.measure_shadow_work or integrator.measure_heat):
+            raise ValueError("implicit solvent together with measure_shadow_work / measure_heat is not supported: the energy ledger's "
+                             "device-side energy sum does not know the GB partials")
+        if int(gb.model) not in (GB_OBC1, GB_OBC2):
+            raise ValueError("implicit solvent: model %d; the engine knows 1 (OBC1) and 2 (OBC2)" % int(gb.model))
+        if int(self.nonbonded_method) != NB_NOCUTOFF:
+            raise ValueError("implicit solvent needs nonbonded_method = NoCutoff: GB has no periodic or cutoff form here")
+        if gb.radius is None or gb.scale is None:
+            raise ValueError("implicit solvent without its radius / scale arrays")
+        radius, scale = np.asarray(gb.radius, dtype=np.float64).reshape(-1), np.asarray(gb.scale, dtype=np.float64).reshape(-1)
+        if len(radius) != self.n_atoms or len(scale) != self.n_atoms:
+            raise ValueError("implicit solvent: %d radii and %d scale factors for %d atoms" % (len(radius), len(scale), self.n_atoms))
+        if not (gb.solute_dielectric > 0.0 and gb.solvent_dielectric > 0.0):
+            raise ValueError("implicit solvent: the dielectric constants must be positive (solute %g, solvent %g)" % (gb.solute_dielectric, gb.solvent_dielectric))
+        if not gb.surface_area_energy >= 0.0:
+            raise ValueError("implicit solvent: surface_area_energy %g is negative" % gb.surface_area_energy)
+        bad = np.nonzero(~(radius > GB_RADIUS_OFFSET))[0]
+        if len(bad):
+            raise ValueError("implicit solvent: radius %g nm of atom %d is not above the 0.009 nm offset" % (radius[bad[0]], bad[0]))
+        if not np.all(np.isfinite(scale)) or np.any(scale < 0.0):
+            raise ValueError("implicit solvent: a scale factor is negative or not finite")
+        if int(self.custom_pair_mode) != PAIR_STANDARD or tuple(self.centroid_bonds or ()):
+            raise ValueError("implicit solvent together with the custom forces (custom_pair_mode, centroid bonds) is not supported")
+        if not self.annihilate_electrostatics:
+            raise ValueError("implicit solvent needs annihilate_electrostatics = 1: the GB charges of the alchemical atoms are scaled by lambda_electrostatics as a whole")
 
     def to_desc(self):
         """Returns (BluesSystemDesc, keepalive) -- keepalive owns the numpy buffers."""
@@ -282,6 +353,7 @@ def declare_engine_prototypes(lib):
     H = C.c_void_p
     protos = {
         "blues_engine_create": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.c_int, C.POINTER(H)], C.c_int),
+        "blues_engine_create_gb": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_int, C.POINTER(H)], C.c_int),
         "blues_engine_destroy": ([H], C.c_int),
         "blues_last_error": ([H], C.c_char_p),
         "blues_abi_version": ([], C.c_int),
@@ -347,7 +419,7 @@ def declare_engine_prototypes(lib):
 
 
 ENGINE_SYMBOLS = (
-    "blues_engine_create", "blues_engine_destroy", "blues_last_error", "blues_abi_version",
+    "blues_engine_create", "blues_engine_create_gb", "blues_engine_destroy", "blues_last_error", "blues_abi_version",
     "blues_tuning_default", "blues_set_tuning", "blues_get_tuning",
     "blues_set_positions", "blues_set_velocities", "blues_set_box", "blues_get_positions",
     "blues_get_velocities", "blues_get_forces", "blues_get_box", "blues_set_velocities_to_temperature",

@@ -127,7 +127,9 @@ def ewald_alpha(cutoff, tolerance):
 
 def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.005, constraints="HBonds",
                       rigid_water=True, hydrogen_mass=None, remove_cm_motion=True, alchemical_atoms=(),
-                      tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME"):
+                      tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME",
+                      implicit_solvent=None, solute_dielectric=1.0, solvent_dielectric=78.5, implicit_solvent_kappa=None,
+                      implicit_solvent_salt_conc=None):
     """Amber topology -> SystemData, following structure.createSystem's kwargs
     (reference examples/rotmove_cuda.yml:19-27: PME, 10 A cutoff, HBonds,
     rigidWater, removeCMMotion, hydrogenMass 3.024, ewaldErrorTolerance 0.005).
@@ -137,10 +139,31 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     excluded-pair corrections, dispersion correction); False keeps the direct-space sum only and says so in the log --
     forces on the water then differ from the reference's, only the protocol work (lambda-dependent pairs) does not.
     nonbonded_method="NoCutoff" (vacuum, reference blues/tests/test_sidechain.py:42): every pair counts, no cutoff, no periodicity,
-    no mesh and no dispersion correction; `box` may be None (the box is then stored as zeros and has no effect)."""
+    no mesh and no dispersion correction; `box` may be None (the box is then stored as zeros and has no effect).
+    implicit_solvent="OBC1" | "OBC2" (createSystem(implicitSolvent=app.OBC1 / app.OBC2, soluteDielectric, solventDielectric), reference
+    blues/simulation.py:139-219): GB-OBC with the ACE surface term on a NoCutoff System, radii from %FLAG RADII and scale factors
+    from %FLAG SCREEN.  HCT, GBn, GBn2 and salt screening (kappa, a salt concentration) are not implemented and raise."""
     if nonbonded_method not in ("PME", "NoCutoff"):
         raise ValueError("nonbonded_method must be 'PME' or 'NoCutoff', got %r" % (nonbonded_method,))
     no_cutoff = nonbonded_method == "NoCutoff"
+    gb = None
+    if implicit_solvent is not None:
+        from ._abi import GB_MODELS, ImplicitSolventData
+        name = getattr(implicit_solvent, "name", implicit_solvent)
+        if name not in GB_MODELS:
+            raise ValueError("implicit_solvent %r is not supported: the engine implements 'OBC1' and 'OBC2' (not HCT, GBn or GBn2)" % (implicit_solvent,))
+        if implicit_solvent_kappa is not None or implicit_solvent_salt_conc is not None:
+            raise ValueError("salt screening (implicit_solvent_kappa, implicit_solvent_salt_conc) is not supported: the engine implements "
+                             "'OBC1' and 'OBC2' without it")
+        if not no_cutoff:
+            raise ValueError("implicit_solvent needs nonbonded_method='NoCutoff': GB has no periodic or cutoff form here")
+        if "RADII" not in prm or "SCREEN" not in prm:
+            raise ValueError("implicit_solvent needs the %FLAG RADII and %FLAG SCREEN sections of the prmtop")
+        gb = ImplicitSolventData(GB_MODELS[name], np.asarray(prm["RADII"], dtype=np.float64) * 0.1, np.asarray(prm["SCREEN"], dtype=np.float64).copy(),
+                                 float(solute_dielectric), float(solvent_dielectric))
+    elif implicit_solvent_kappa is not None or implicit_solvent_salt_conc is not None:
+        raise ValueError("implicit_solvent_kappa / implicit_solvent_salt_conc without implicit_solvent (and salt screening is not supported: "
+                         "the engine implements 'OBC1' and 'OBC2' without it)")
     if box is None:
         if not no_cutoff:
             raise ValueError("a periodic System (nonbonded_method='PME') needs a box")
@@ -163,6 +186,12 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     is_water_res = np.array([lab in WATER_NAMES for lab in res_lab])
     is_water = is_water_res[residue_of_atom]
 
+    if gb is not None and tip3p_for_untyped_water:
+        # water written without types carries no GB parameters either (RADII = SCREEN = 0): it gets what tleap's mbondi set gives a
+        # water molecule [recalled: O 1.5 A, H bonded to O 0.8 A; screen 0.85 for both], as it gets TIP3P's Lennard-Jones below
+        blank = is_water & (gb.radius == 0.0) & (gb.scale == 0.0)
+        gb.radius[blank] = np.where(atnum[blank] == 8, 0.15, 0.08)
+        gb.scale[blank] = 0.85
     sigma = np.zeros(natom)
     eps = np.zeros(natom)
     for i in range(natom):
@@ -282,7 +311,7 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
         logging.getLogger(__name__).warning("system_from_amber: PME lowered to its direct-space part (reciprocal_space=False): no mesh, self or "
                                             "dispersion terms; energies and environment forces are not those of nonbondedMethod=PME")
         method, grid = NB_PME_DIRECT, (0, 0, 0)
-    return SystemData(
+    system = SystemData(
         pme_grid=grid, pme_order=5, dispersion_correction=bool(dispersion_correction),
         box=np.asarray(box, dtype=np.float64), mass=mass, charge=charge, sigma=sigma, epsilon=eps,
         exclusions=excl,
@@ -296,4 +325,7 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
         nonbonded_method=method, cutoff=cutoff, ewald_alpha=alpha,
         remove_cm_motion=remove_cm_motion, positions=np.asarray(positions, dtype=np.float64),
         residue_of_atom=residue_of_atom, names=list(prm.get("ATOM_NAME", [])),
+        implicit_solvent=gb,
     )
+    system.check_implicit_solvent()
+    return system

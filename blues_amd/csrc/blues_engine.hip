@@ -39,6 +39,7 @@
 #include "kernels_pme.h"
 #include "kernels_batch.h"
 #include "kernels_nocutoff.h"
+#include "kernels_gb.h"
 static_assert(CENT_GROUP == BLUES_MAX_CENTROID_GROUP, "a centroid-bond term has one place per atom the C-ABI allows in a group (kernels_bonded.h, build_bonded)");
 static_assert(T_CENT >= T_NTYPES, "T_CENT is an entry type only: it has no slot in the per-type arrays");
 
@@ -286,6 +287,10 @@ struct BluesEngine {
     int k1_iw = 64;  // i-atoms per wave in the nonbonded kernel: 64 = classic tile kernel, 8/16 = sub-tile throughput kernel
     int k1_mode = 0;  // 0: tile kernel (lane = i-atom), 1: sub-tile kernel, 2: per-atom Verlet lists + LDS tile image (nonbonded_atom_body), 3: fragment lists (kernels_frag.h), 4: all pairs of a NoCutoff System (kernels_nocutoff.h)
     int pair_mode = 0;   // BLUES_PAIR_*: 1 = the alchemical x environment pairs take the form of kernels_alch.h FORM 1 and are the only nonbonded pairs (NoCutoff)
+    // implicit solvent (kernels_gb.h, NoCutoff only): model (BLUES_GB_*; 0: none), its constants, per-atom parameters and the three passes' buffers (nocut_layout)
+    int gb_model = 0, gb_blocks = 0; double gb_pref = 0.0, gb_sa = 0.0, gb_eps_in = 1.0, gb_eps_out = 78.5, gb_sa_energy = 0.0; std::vector<double> gb_radius, gb_scale;
+    DBuf<GbArgs> d_gb_rec; long long gb_rec_epoch = -1;   // a lone engine's own record for the kernels (launch_gb)
+    DBuf<double4> d_gbpar; DBuf<int> d_gb_alch; DBuf<double> d_gb_born, d_gb_G, d_gb_fdir, d_fgb, d_gb_epart;
     DBuf<double4> d_ncpar; int nc_blocks_f = 0, nc_blocks_e = 0;   // NoCutoff: per-atom parameters, blocks of the force / energy launches (nocut_layout)
     // fragment lists (every environment atom mobile): the static cut of the environment into fragments of <= 3 atoms
     // (build_fragments), the layout of the current sort, the lists
@@ -409,6 +414,7 @@ struct BluesBatch {
     struct EvPair { hipEvent_t a = nullptr, b = nullptr; bool busy = false; };
     std::vector<const BluesEngine*> congr_lead; std::vector<uint64_t> congr_le, congr_me;   // congruence already established (batch_do_steps)
     bool defer_work = false; std::vector<DevAccum*> h_wacc; std::vector<double> h_wdelta; DBuf<DevAccum*> d_wacc; DBuf<double> d_wdelta;   // add_work of all members in one launch
+    DBuf<GbArgs> d_gb;   // NoCutoff members with implicit solvent: the records of kernels_gb.h (batch_refresh_args)
     DBuf<NcArgs> d_nc;   // NoCutoff members: the records of the all-pairs kernel (batch_refresh_args)
     std::vector<EvPair> k1t_pairs; int k1t_every = 0; int64_t k1t_seen = 0, k1t_n = 0; double k1t_sum_us = 0.0, k1t_max_us = 0.0;
     int R() const { return (int)eng.size(); }
@@ -968,6 +974,14 @@ static int nocut_layout(BluesEngine* h) {
           h->d_finrecs.upload(fr); }
         h->d_fJ.alloc((size_t)9 * n);
         h->d_self_part.alloc((size_t)(h->k2_nblocks_env + 1) * 9 * 64); h->d_e_part.alloc((size_t)(h->k2_nblocks_env + 1) * K2_NP); h->d_mom_part.alloc((size_t)(h->n_islots / 64 + 2) * 6);
+        if (h->gb_model) {   // implicit solvent: every atom is an i-atom of its three passes (frozen atoms descreen and carry a Born radius)
+            h->gb_blocks = (n + GB_THREADS - 1) / GB_THREADS;
+            std::vector<double4> gp(n); std::vector<int> ga(n);
+            for (int i = 0; i < n; i++) { const double o = h->gb_radius[i] - 0.009; gp[i] = make_double4(h->T->charge[i], o, h->gb_scale[i] * o, h->gb_radius[i]); ga[i] = h->T->alch_local[i] >= 0; }
+            h->d_gbpar.upload(gp); h->d_gb_alch.upload(ga);
+            h->d_gb_born.alloc((size_t)2 * n); h->d_gb_G.alloc((size_t)3 * n); h->d_gb_fdir.alloc((size_t)9 * n); h->d_fgb.alloc((size_t)9 * n);
+            h->d_gb_epart.alloc((size_t)h->gb_blocks * GB_NE);
+        }
     } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
     // no frozen-frozen constant: the all-pairs energy kernel has every pair
     h->e_frozen[0] = h->e_frozen[1] = 0.0; h->e_frozen_valid = true;
@@ -1678,6 +1692,42 @@ template <typename R, bool ENERGY> static int launch_nocut(BluesEngine* h) {
     return 0;
 }
 
+// implicit solvent (kernels_gb.h): Born radii, pairs, chain term; the energy form stops after the pairs' energy partials
+static GbArgs make_gb_args(BluesEngine* h) {
+    GbArgs a; memset(&a, 0, sizeof a);
+    a.active = 1; a.n = h->n;
+    for (int k = 0; k < 3; k++) a.x[k] = h->d_x[k].p;
+    a.par = h->d_gbpar.p; a.alch = h->d_gb_alch.p; a.mass = h->d_mass.p;
+    if (h->gb_model == BLUES_GB_OBC1) { a.alpha = 0.8; a.beta = 0.0; a.gamma = 2.909125; } else { a.alpha = 1.0; a.beta = 0.8; a.gamma = 4.85; }
+    a.pref = h->gb_pref; a.sa = h->gb_sa;
+    a.born = h->d_gb_born.p; a.G = h->d_gb_G.p; a.fdir = h->d_gb_fdir.p; a.fgb = h->d_fgb.p; a.epart = h->d_gb_epart.p;
+    return a;
+}
+template <typename R, bool ENERGY> static int launch_gb(BluesEngine* h, const double le[3]) {
+    const int nb = h->gb_blocks;
+    GbDyn d; for (int s = 0; s < 3; s++) d.le[s] = le[s];
+    if (batch_lead(h)) {
+        const dim3 grid(nb, h->batch->R());
+        hipLaunchKernelGGL((k_gb_born_b<R>), grid, dim3(GB_THREADS), 0, h->cur, h->batch->d_gb.p);
+        hipLaunchKernelGGL((k_gb_pairs_b<R, ENERGY>), grid, dim3(GB_THREADS), 0, h->cur, h->batch->d_gb.p);
+        if (!ENERGY) hipLaunchKernelGGL((k_gb_chain_b<R>), grid, dim3(GB_THREADS), 0, h->cur, h->batch->d_gb.p, d);
+    } else if (!batch_dry(h)) {   // (a lone chain: the same kernels over its own record, refreshed when a layout has changed its buffers)
+        if (h->gb_rec_epoch != (long long)h->args_epoch) {
+            std::vector<GbArgs> rec(1, make_gb_args(h));
+            HIP_OK(h, hipStreamSynchronize(h->cur));
+            try { h->d_gb_rec.upload(rec); } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+            h->gb_rec_epoch = (long long)h->args_epoch;
+        }
+        hipLaunchKernelGGL((k_gb_born_b<R>), dim3(nb, 1), dim3(GB_THREADS), 0, h->cur, h->d_gb_rec.p);
+        hipLaunchKernelGGL((k_gb_pairs_b<R, ENERGY>), dim3(nb, 1), dim3(GB_THREADS), 0, h->cur, h->d_gb_rec.p);
+        if (!ENERGY) hipLaunchKernelGGL((k_gb_chain_b<R>), dim3(nb, 1), dim3(GB_THREADS), 0, h->cur, h->d_gb_rec.p, d);
+    }
+    h->st_launches += ENERGY ? 2 : 3;
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+template <bool ENERGY> static int launch_gb_p(BluesEngine* h, const double le[3]) { return h->precision == 0 ? launch_gb<float, ENERGY>(h, le) : launch_gb<double, ENERGY>(h, le); }
+
 template <typename R, bool ENERGY> static int launch_nonbonded(BluesEngine* h) {
     if (h->k1_mode == 4) return launch_nocut<R, ENERGY>(h);
     NbArgs<R> a = make_nb_args<R>(h);
@@ -1894,6 +1944,7 @@ static FinArgs make_fin_args(BluesEngine* h, const double le[3], int slot_mask =
     for (int k = 0; k < 3; k++) F.v[k] = h->d_v[k].p;
     F.mass = h->d_mass.p; F.mom_part = h->d_mom_part.p;
     F.frec = h->pme ? h->d_frec.p : nullptr;
+    if (h->gb_model) { F.fgb = h->d_fgb.p; F.gb_epart = h->d_gb_epart.p; F.gb_blocks = h->gb_blocks; }
     return F;
 }
 
@@ -2320,6 +2371,7 @@ static int force_pass(BluesEngine* h, int base_L) {
         if (rc || launch_pme(h, 0)) return 1;
         if (!fused && launch_bonded(h, true)) return 1;
     }
+    if (h->gb_model && launch_gb_p<false>(h, le)) return 1;   // (implicit solvent: a NoCutoff engine takes the serial schedule above)
     if (launch_finalize_deferred(h, le, fmask)) return 1;
     h->pass_valid = true; h->pass_L = base_L; h->st_passes++; h->vel_clean = true; h->acc_cache_valid = false;
     HIP_OK(h, hipGetLastError());
@@ -2443,6 +2495,7 @@ static int energy_launch(BluesEngine* h) {
     if (launch_alchemical(h, ls, le, 1)) return 1;
     rc = launch_nonbonded_p<true>(h);
     if (rc) return 1;
+    if (h->gb_model && launch_gb_p<true>(h, le)) return 1;
     if (launch_pme(h, 1)) return 1;
     const EnergyShape g = energy_shape(h);
     if (g.nbb > 0) {
@@ -2460,7 +2513,8 @@ static int energy_launch(BluesEngine* h) {
 // the host-side sums over the partials, in a fixed order (the same whether they were downloaded one engine at a time or
 // gathered for a whole batch)
 // one[2] (optional): the two alchemical terms at lambda_sterics = lambda_electrostatics = 1 (slot 1 of the same pass)
-static void energy_sum(BluesEngine* h, const double* enb, const double* eb, int jcount_alch, const double* ep, double e_mesh, double T[BLUES_N_ENERGY_TERMS], double* one = nullptr) {
+// egb (implicit solvent only): the GB partials [gb_blocks][GB_NE]; one[2], one[3] then carry terms [8], [9] at lambda_electrostatics = 1
+static void energy_sum(BluesEngine* h, const double* enb, const double* eb, int jcount_alch, const double* ep, double e_mesh, double T[BLUES_N_ENERGY_TERMS], double* one = nullptr, const double* egb = nullptr) {
     const EnergyShape g = energy_shape(h);
     for (int t = 0; t < BLUES_N_ENERGY_TERMS; t++) T[t] = 0.0;
     double e_nb = 0.0; for (int w = 0; w < g.nw; w++) e_nb += enb[2 * w] + enb[2 * w + 1];
@@ -2474,13 +2528,20 @@ static void energy_sum(BluesEngine* h, const double* enb, const double* eb, int 
         T[5] = s[1] + s[4]; T[6] = h->cur_le * s[0] + s[5];
         if (one) { one[0] = s[2] + s[4]; one[1] = 1.0 * s[0] + s[5]; }
     } else if (one) { one[0] = 0.0; one[1] = 0.0; }
+    if (h->gb_model && egb) {   // E(le) = E0 + le E1 + le^2 E2 (kernels_gb.h), the blocks' partials in block order
+        double c[GB_NE] = {0, 0, 0, 0, 0, 0};
+        for (int b = 0; b < h->gb_blocks; b++) for (int q = 0; q < GB_NE; q++) c[q] += egb[(size_t)b * GB_NE + q];
+        const double le = h->cur_le;
+        T[8] = c[0] + le * (c[1] + le * c[2]); T[9] = c[3] + le * c[4];
+        if (one) { one[2] = c[0] + (c[1] + c[2]); one[3] = c[3] + c[4]; }
+    } else if (one) { one[2] = T[8]; one[3] = T[9]; }
 }
 
 // total at the current parameters and, from the same terms, at lambda = (1, 1): summed in term order, as a direct evaluation at
 // those parameters would (so the cached value is the one that evaluation returns)
-static void energy_totals(BluesEngine* h, const double T[BLUES_N_ENERGY_TERMS], const double one[2], double* E, double* E_one) {
+static void energy_totals(BluesEngine* h, const double T[BLUES_N_ENERGY_TERMS], const double one[4], double* E, double* E_one) {
     *E = 0.0; *E_one = 0.0;
-    for (int t = 0; t < BLUES_N_ENERGY_TERMS; t++) { *E += T[t]; *E_one += (t == 5) ? one[0] : (t == 6 ? one[1] : T[t]); }
+    for (int t = 0; t < BLUES_N_ENERGY_TERMS; t++) { *E += T[t]; *E_one += (t == 5) ? one[0] : (t == 6 ? one[1] : (t == 8 ? one[2] : (t == 9 ? one[3] : T[t]))); }
     (void)h;
 }
 
@@ -2500,8 +2561,9 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
         h->st_launches += 2;
     }
     if (check_flags(h)) return 1;
-    std::vector<double> enb, eb, ep; std::vector<int> jc;
+    std::vector<double> enb, eb, ep, egb; std::vector<int> jc;
     try {
+        if (h->gb_model) h->d_gb_epart.download(egb);
         h->d_epart_nb.download(enb);
         if (!h->e_frozen_valid) {
             h->e_frozen[0] = h->e_frozen[1] = 0.0;
@@ -2513,8 +2575,8 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
     } catch (std::string& msg) { E_FAIL(h, "%s", msg.c_str()); }
     double e_mesh = 0.0;
     if (h->pme) HIP_OK(h, hipMemcpy(&e_mesh, h->d_pme_e.p, sizeof e_mesh, hipMemcpyDeviceToHost));
-    double one[2], E, E_one;
-    energy_sum(h, enb.data(), eb.data(), h->alch.empty() ? 0 : jc[h->n_lists], ep.data(), e_mesh, T, one);
+    double one[4], E, E_one;
+    energy_sum(h, enb.data(), eb.data(), h->alch.empty() ? 0 : jc[h->n_lists], ep.data(), e_mesh, T, one, h->gb_model ? egb.data() : nullptr);
     energy_totals(h, T, one, &E, &E_one);
     h->ecache.put(1.0, 1.0, E_one); h->ecache.put(h->cur_ls, h->cur_le, E);   // (the current parameters last: they win when both are (1, 1))
     return 0;
@@ -2864,6 +2926,8 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
     if (nocut(a) != nocut(b)) { *why = "nonbonded method (a NoCutoff engine and a periodic one cannot share a batch)"; return false; }
     if (a->led_flags != b->led_flags) { *why = "measure_shadow_work / measure_heat (measuring and non-measuring members cannot share a batch)"; return false; }
     if (a->pair_mode != b->pair_mode || a->n_cent != b->n_cent) { *why = "custom forces (members with and without the custom pair form or centroid bonds cannot share a batch)"; return false; }
+    if ((a->gb_model != 0) != (b->gb_model != 0)) { *why = "implicit solvent (members with and without it cannot share a batch)"; return false; }
+    if (a->gb_model != b->gb_model || a->gb_eps_in != b->gb_eps_in || a->gb_eps_out != b->gb_eps_out || a->gb_sa_energy != b->gb_sa_energy || a->gb_radius != b->gb_radius || a->gb_scale != b->gb_scale) { *why = "implicit solvent (model, dielectrics, surface term, radii or scales differ)"; return false; }
 #define BC(f) if (a->f != b->f) { *why = #f; return false; }
     BC(device) BC(n) BC(precision) BC(nsteps) BC(nprop) BC(n_lambda) BC(split) BC(remove_cm) BC(dt) BC(gamma) BC(kT) BC(tol) BC(prop_min) BC(prop_max)
     BC(n_itiles) BC(n_tiles) BC(jcap) BC(n_islots) BC(pool_cap) BC(PA) BC(k2_nblocks_env) BC(k2_jiter) BC(seg_len) BC(waves_tile) BC(wpb) BC(npart)
@@ -2906,6 +2970,8 @@ static int batch_refresh_args(BluesBatch* B) {
     std::vector<RepCore> core(B->R()); std::vector<RepNb<float>> nf; std::vector<RepNb<double>> nd;
     const bool no_cutoff = nocut(B->eng[0]);
     std::vector<NcArgs> nc(no_cutoff ? B->R() : 0);
+    const bool with_gb = B->eng[0]->gb_model != 0;
+    std::vector<GbArgs> gb(with_gb ? B->R() : 0);
     const bool single = B->eng[0]->precision == 0;
     if (single) nf.resize(B->R()); else nd.resize(B->R());
     for (int r = 0; r < B->R(); r++) {
@@ -2915,6 +2981,7 @@ static int batch_refresh_args(BluesBatch* B) {
         B->rec_delta[r] = h->h_draw - lead->h_draw; core[r].draw_delta = B->rec_delta[r];
         if (single) nf[r].active = B->rec_active[r]; else nd[r].active = B->rec_active[r];
         if (no_cutoff) { nc[r] = make_nc_args(h); nc[r].active = B->rec_active[r] && h->sorted_ok; }
+        if (with_gb) { gb[r] = make_gb_args(h); gb[r].active = B->rec_active[r] && h->sorted_ok; }
         if (!h->sorted_ok) { core[r].active = 0; if (single) nf[r].active = 0; else nd[r].active = 0; continue; }  // buffers not laid out (its sort failed): never touched
         core[r].al = make_alch_args(h, one, one, 7); core[r].bo = make_bonded_args(h); core[r].fin = make_fin_args(h, one); core[r].in = make_int_args(h);
         core[r].in.work_trace = h->d_trace.p;  // the launch decides whether it is written (IntDyn.tracing)
@@ -2925,7 +2992,7 @@ static int batch_refresh_args(BluesBatch* B) {
     }
     // the records may be in use by launches still in flight
     if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-    try { B->d_core.upload(core); if (single) B->d_nb_f.upload(nf); else B->d_nb_d.upload(nd); if (no_cutoff) B->d_nc.upload(nc); } catch (std::string& e) { B->err = e; return 1; }
+    try { B->d_core.upload(core); if (single) B->d_nb_f.upload(nf); else B->d_nb_d.upload(nd); if (no_cutoff) B->d_nc.upload(nc); if (with_gb) B->d_gb.upload(gb); } catch (std::string& e) { B->err = e; return 1; }
     return 0;
 }
 
@@ -3014,12 +3081,12 @@ static bool prefetch_potential(BluesBatch* B, BluesEngine* lead, std::vector<cha
     if (batch_section_begin(B, lead)) return false;
     bool ok = batch_each(B, true, [&](int r) { return live[r] != 0; }, [&](int r) { return energy_launch(B->eng[r]); }) < 0;
     const EnergyShape g = energy_shape(lead);
-    const int n_nb = 2 * g.nw, n_b = g.nbb * T_NTYPES, n_al = lead->alch.empty() ? 0 : (lead->k2_nblocks_env + 1) * K2_NP, stride = n_nb + n_b + n_al + 2;
+    const int n_nb = 2 * g.nw, n_b = g.nbb * T_NTYPES, n_al = lead->alch.empty() ? 0 : (lead->k2_nblocks_env + 1) * K2_NP, n_gb = lead->gb_model ? lead->gb_blocks * GB_NE : 0, stride = n_nb + n_b + n_al + 2 + n_gb;
     std::vector<double> slab; std::vector<int> hints;
     try {
         if (ok) {
             if (B->d_gather.n != (size_t)R * stride) B->d_gather.alloc((size_t)R * stride);
-            by_precision(lead->precision, [&](auto tag) { using T = decltype(tag); hipLaunchKernelGGL(k_gather_energy_parts_b<T>, dim3(R), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_core.p, n_nb, n_b, n_al, stride, B->d_gather.p); });
+            by_precision(lead->precision, [&](auto tag) { using T = decltype(tag); hipLaunchKernelGGL(k_gather_energy_parts_b<T>, dim3(R), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_core.p, n_nb, n_b, n_al, n_gb, stride, B->d_gather.p); });
             batch_launch_hints(B);
             ok = hipStreamSynchronize(B->stream) == hipSuccess;
             if (ok) { B->d_gather.download(slab); batch_read_hints(B, hints); }
@@ -3028,8 +3095,8 @@ static bool prefetch_potential(BluesBatch* B, BluesEngine* lead, std::vector<cha
     if (ok) for (int r = 0; r < R; r++) if (live[r] && !(hints[r] & 2)) {   // a member with an error flag keeps no cached value: its own call will report
         BluesEngine* m = B->eng[r];
         const double* o = slab.data() + (size_t)r * stride;
-        double T[BLUES_N_ENERGY_TERMS], one[2], E, E_one;
-        energy_sum(m, o, o + n_nb, (int)o[n_nb + n_b + n_al], o + n_nb + n_b, o[n_nb + n_b + n_al + 1], T, one);
+        double T[BLUES_N_ENERGY_TERMS], one[4], E, E_one;
+        energy_sum(m, o, o + n_nb, (int)o[n_nb + n_b + n_al], o + n_nb + n_b, o[n_nb + n_b + n_al + 1], T, one, n_gb ? o + n_nb + n_b + n_al + 2 : nullptr);
         energy_totals(m, T, one, &E, &E_one);
         m->ecache.put(1.0, 1.0, E_one); m->ecache.put(m->cur_ls, m->cur_le, E);
     }
@@ -3293,7 +3360,25 @@ int blues_get_tuning(BluesTuning* t) { *t = g_tuning; return 0; }
 
 const char* blues_last_error(const BluesEngine* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it) {
+static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb) {
+    if (gb && gb->model != BLUES_GB_NONE) {   // implicit solvent (kernels_gb.h): what such an engine refuses, each with its reason
+        if (gb->model != BLUES_GB_OBC1 && gb->model != BLUES_GB_OBC2) E_FAIL(h, "implicit solvent: model %d; the engine knows 1 (OBC1) and 2 (OBC2)", gb->model);
+        if (s->nonbonded_method != BLUES_NB_NOCUTOFF) E_FAIL(h, "implicit solvent needs nonbonded_method = NoCutoff: GB has no periodic or cutoff form here");
+        if (!gb->radius || !gb->scale) E_FAIL(h, "implicit solvent without its radius / scale arrays");
+        if (!(gb->solute_dielectric > 0.0) || !(gb->solvent_dielectric > 0.0)) E_FAIL(h, "implicit solvent: the dielectric constants must be positive (solute %g, solvent %g)", gb->solute_dielectric, gb->solvent_dielectric);
+        if (!(gb->surface_area_energy >= 0.0)) E_FAIL(h, "implicit solvent: surface_area_energy %g is negative", gb->surface_area_energy);
+        for (int i = 0; i < s->n_atoms; i++) {
+            if (!(gb->radius[i] > 0.009)) E_FAIL(h, "implicit solvent: radius %g nm of atom %d is not above the 0.009 nm offset", gb->radius[i], i);
+            if (!(gb->scale[i] >= 0.0) || !std::isfinite(gb->scale[i])) E_FAIL(h, "implicit solvent: scale factor %g of atom %d", gb->scale[i], i);
+        }
+        if (s->custom_pair_mode != BLUES_PAIR_STANDARD || s->n_centroid_bonds != 0) E_FAIL(h, "implicit solvent together with the custom forces (custom_pair_mode, centroid bonds) is not supported");
+        if (!s->annihilate_electrostatics) E_FAIL(h, "implicit solvent needs annihilate_electrostatics = 1: the GB charges of the alchemical atoms are scaled by lambda_electrostatics as a whole");
+        if (it->measure_shadow_work || it->measure_heat) E_FAIL(h, "implicit solvent together with measure_shadow_work / measure_heat is not supported: the energy ledger's device-side energy sum does not know the GB partials");
+        h->gb_model = gb->model; h->gb_eps_in = gb->solute_dielectric; h->gb_eps_out = gb->solvent_dielectric; h->gb_sa_energy = gb->surface_area_energy;
+        h->gb_pref = ONE_4PI_EPS0 * (1.0 / gb->solute_dielectric - 1.0 / gb->solvent_dielectric);
+        h->gb_sa = 4.0 * 3.14159265358979323846 * gb->surface_area_energy;
+        h->gb_radius.assign(gb->radius, gb->radius + s->n_atoms); h->gb_scale.assign(gb->scale, gb->scale + s->n_atoms);
+    }
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) if (r != c && s->box[3 * r + c] != 0.0) E_FAIL(h, "only orthorhombic boxes are supported");
     if (s->nonbonded_method != BLUES_NB_PME_DIRECT && s->nonbonded_method != BLUES_NB_PME && s->nonbonded_method != BLUES_NB_NOCUTOFF) E_FAIL(h, "unknown nonbonded_method %d", s->nonbonded_method);
     const bool no_cutoff = s->nonbonded_method == BLUES_NB_NOCUTOFF;
@@ -3478,7 +3563,8 @@ int blues_debug_check_guards(int64_t* out8) {
 }
 int blues_debug_setup_seconds(double* out8) { if (!out8) return 2; for (int k = 0; k < 8; k++) out8[k] = g_setup_sec[k]; return 0; }
 
-int blues_engine_create(const BluesSystemDesc* s, const BluesIntegratorDesc* it, int device, BluesEngine** out) {
+int blues_engine_create(const BluesSystemDesc* s, const BluesIntegratorDesc* it, int device, BluesEngine** out) { return blues_engine_create_gb(s, it, nullptr, device, out); }
+int blues_engine_create_gb(const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, int device, BluesEngine** out) {
     SetupTimer tm_create(0);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available: the blues_amd engine has no CPU fallback"; return 2; }
@@ -3486,7 +3572,7 @@ int blues_engine_create(const BluesSystemDesc* s, const BluesIntegratorDesc* it,
     BluesEngine* h = new BluesEngine();
     h->device = device;
     int rc;
-    try { rc = create_impl(h, s, it); } catch (std::string& e) { h->err = e; rc = 1; }
+    try { rc = create_impl(h, s, it, gb); } catch (std::string& e) { h->err = e; rc = 1; }
     if (rc) { g_create_error = h->err; delete h; return rc; }
     *out = h;
     return 0;
@@ -3869,6 +3955,7 @@ int blues_get_forces(BluesEngine* h, double* out, int32_t n_atoms) {
     rc = launch_nonbonded_p<false>(h);
     if (rc) return 1;
     if (launch_pme(h, 0)) return 1;
+    if (h->gb_model && launch_gb_p<false>(h, le)) return 1;
     if (launch_bonded_and_finalize(h, le, false)) return 1;
     IntArgs A = make_int_args(h);
     DBuf<double> tmp;
@@ -4410,6 +4497,7 @@ int blues_batch_create(BluesEngine* const* engines, int32_t count, BluesBatch** 
         if (engines[r]->switch_mode != BLUES_SWITCH_NONE) { g_batch_create_error = "the switching integrators (switching_mode != 0) step one engine at a time: their energy bookkeeping is synchronous"; return 2; }
         for (int q = 0; q < r; q++) if (engines[q] == engines[r]) { g_batch_create_error = "duplicate engine handle"; return 2; }
         if (nocut(engines[r]) != nocut(engines[0])) { g_batch_create_error = "a batch cannot mix NoCutoff (non-periodic) engines with periodic ones"; return 2; }
+        if ((engines[r]->gb_model != 0) != (engines[0]->gb_model != 0)) { g_batch_create_error = "a batch cannot mix members with and without implicit solvent"; return 2; }
         if (engines[r]->pair_mode != engines[0]->pair_mode || engines[r]->n_cent != engines[0]->n_cent) { g_batch_create_error = "a batch cannot mix engines with and without custom forces (custom pair form, centroid bonds)"; return 2; }
     }
     BluesBatch* B = new BluesBatch();

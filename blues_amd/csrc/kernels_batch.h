@@ -468,7 +468,7 @@ __global__ void __launch_bounds__(64) k_sum_frozen_b(const RepNb<R>* __restrict_
 }
 
 template <typename R>
-__global__ void __launch_bounds__(256) k_gather_energy_parts_b(const RepNb<R>* __restrict__ rnb, const RepCore* __restrict__ reps, int n_nb, int n_b, int n_alch, int stride, double* out) {
+__global__ void __launch_bounds__(256) k_gather_energy_parts_b(const RepNb<R>* __restrict__ rnb, const RepCore* __restrict__ reps, int n_nb, int n_b, int n_alch, int n_gb, int stride, double* out) {
     const int r = blockIdx.x;
     if (!reps[r].active) return;
     double* o = out + (size_t)r * stride;
@@ -477,5 +477,6 @@ __global__ void __launch_bounds__(256) k_gather_energy_parts_b(const RepNb<R>* _
     for (int k = threadIdx.x; k < n_b; k += 256) o[n_nb + k] = eb[k];
     for (int k = threadIdx.x; k < n_alch; k += 256) o[n_nb + n_b + k] = ep[k];
     if (threadIdx.x == 0) o[n_nb + n_b + n_alch] = n_alch > 0 ? (double)*reps[r].al.jcount : 0.0;
+    for (int k = threadIdx.x; k < n_gb; k += 256) o[n_nb + n_b + n_alch + 2 + k] = reps[r].fin.gb_epart[k];   // implicit solvent (kernels_gb.h): [gb_blocks][6], behind the two scalars
     if (threadIdx.x == 1 && stride > n_nb + n_b + n_alch + 1) o[n_nb + n_b + n_alch + 1] = rnb[r].pme.n > 0 ? rnb[r].pme.epart[0] : 0.0;   // mesh energy
 }

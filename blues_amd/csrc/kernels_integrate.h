@@ -411,6 +411,10 @@ struct FinArgs {
     // mom_part[block][0..2] = sum m v, [3..5] = sum of the slot-0 force, over the block's atoms
     const double* v[3]; const double* mass; double* mom_part;
     const double* frec;   // [3][n] reciprocal-space force (kernels_pme.h), lambda-independent; null without BLUES_NB_PME
+    // implicit solvent (kernels_gb.h); null / 0 without it, and then nothing below is read or added
+    const double* fgb;        // [9][n] GB force per slot and atom, caller order (every slot is written by every pass)
+    const double* gb_epart;   // [gb_blocks][6] energy partials per class: polar E0, E1, E2, surface E0, E1
+    int gb_blocks;
 };
 
 // grid: [0, n_itiles) one block per i-tile | [n_itiles, +nb_alch_atoms) alchemical atoms' bonded rows |
@@ -457,16 +461,21 @@ __device__ __forceinline__ void finalize_body(FinArgs& A) {
         for (int sl = 0; sl < 3; sl++)
 #pragma unroll
             for (int k = 0; k < 3; k++) fj[sl][k] = (i >= 0 && isl >= 0 && A.n_alch > 0 && ((A.slot_mask >> sl) & 1)) ? A.fJ[(size_t)(sl * 3 + k) * A.n + rec.sorted] : 0.0;
+        double fg[3][3];  // implicit-solvent force on this (environment) atom per slot
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) fg[sl][k] = (A.fgb && i >= 0 && isl >= 0) ? A.fgb[(size_t)(sl * 3 + k) * A.n + i] : 0.0;
         if (i >= 0) {
             fin_atom_base(A.fpart, A.n_islots, A.npart > 1 ? 0 : A.npart, A.fent, A.n_entries, A.frec, A.n, isl, i, rec.e0, rec.e1, f, pre);
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 if (isl >= 0 && A.n_alch > 0) {
 #pragma unroll
-                    for (int sl = 0; sl < 3; sl++) if ((A.slot_mask >> sl) & 1) A.ftot[(size_t)(sl * 3 + k) * A.n + i] = f[k] + fj[sl][k];
+                    for (int sl = 0; sl < 3; sl++) if ((A.slot_mask >> sl) & 1) A.ftot[(size_t)(sl * 3 + k) * A.n + i] = A.fgb ? f[k] + fj[sl][k] + fg[sl][k] : f[k] + fj[sl][k];
                 } else if (isl >= 0) {
 #pragma unroll
-                    for (int sl = 0; sl < 3; sl++) if ((A.slot_mask >> sl) & 1) A.ftot[(size_t)(sl * 3 + k) * A.n + i] = f[k];
+                    for (int sl = 0; sl < 3; sl++) if ((A.slot_mask >> sl) & 1) A.ftot[(size_t)(sl * 3 + k) * A.n + i] = A.fgb ? f[k] + fg[sl][k] : f[k];
                 } else A.ftot[(size_t)k * A.n + i] = f[k];  // alchemical atom: bonded part; integrator adds alch_self[slot]
             }
         }
@@ -476,6 +485,7 @@ __device__ __forceinline__ void finalize_body(FinArgs& A) {
         for (int k = 0; k < 3; k++) {
             pm[k] = i >= 0 ? m * A.v[k][i] : 0.0;
             pm[3 + k] = i >= 0 ? f[k] + ((isl >= 0 && A.n_alch > 0) ? fj[0][k] : 0.0) : 0.0;
+            if (A.fgb) pm[3 + k] += fg[0][k];
         }
 #pragma unroll
         for (int q = 0; q < 6; q++) { pm[q] = wave_sum(pm[q]); if (lane == 0) A.mom_part[(size_t)blk * 6 + q] = pm[q]; }
@@ -489,17 +499,22 @@ __device__ __forceinline__ void finalize_body(FinArgs& A) {
         __shared__ double s_red[256];
         const bool on = (A.slot_mask >> (blk / 3)) & 1;
         const double t = fin_alch_self(A.self_part, A.PA, nb_env, A.k2_nblocks_env, blk, on, A.n_alch, s_red);
-        if (on && tid < A.n_alch) A.alch_self[blk * 64 + tid] = t;
+        if (on && tid < A.n_alch) A.alch_self[blk * 64 + tid] = A.fgb ? t + A.fgb[(size_t)blk * A.n + A.alch_orig[tid]] : t;   // (implicit solvent: the alchemical atoms' share travels with their pair force)
         return;
     }
     __shared__ double s_e[K2_NP];
     fin_energy_sums(A.e_part, nb_env, A.k2_nblocks_env, s_e);
     // (constant indices only: a runtime index into A -- even a select between its fields -- keeps the whole argument
     // struct in scratch memory and turns every A.field access of the kernel into a scratch load)
-    if (tid == 0) A.acc->e_slot[0] = A.le[0] * s_e[0] + s_e[1];
-    if (tid == 1) A.acc->e_slot[1] = A.le[1] * s_e[0] + s_e[2];
-    if (tid == 2) A.acc->e_slot[2] = A.le[2] * s_e[0] + s_e[3];
-    if (tid < 6) A.mom_part[(size_t)(n_itiles + 1) * 6 + tid] = tid < 3 ? 0.0 : s_e[K2_NE + tid - 3];  // alchemical pair force on the alchemical atoms
+    // implicit solvent: the lambda-dependent part of E_GB(le) = E0 + le E1 + le^2 E2 joins the slot's energy (E0 is the same in every
+    // slot and is left out: the work of an H step is formed from what changes); the blocks' partials are added in block order
+    double g1 = 0.0, g2 = 0.0, gf = 0.0;
+    if (A.gb_epart && tid < 3) for (int b = 0; b < A.gb_blocks; b++) { g1 += A.gb_epart[(size_t)b * 6 + 1] + A.gb_epart[(size_t)b * 6 + 4]; g2 += A.gb_epart[(size_t)b * 6 + 2]; }
+    if (A.fgb && tid >= 3 && tid < 6) for (int a = 0; a < A.n_alch; a++) gf += A.fgb[(size_t)(tid - 3) * A.n + A.alch_orig[a]];
+    if (tid == 0) A.acc->e_slot[0] = A.gb_epart ? __fma_rn(A.le[0], __fma_rn(A.le[0], g2, g1), A.le[0] * s_e[0] + s_e[1]) : A.le[0] * s_e[0] + s_e[1];   // (explicit: one rounding order in every kernel that holds this body)
+    if (tid == 1) A.acc->e_slot[1] = A.gb_epart ? __fma_rn(A.le[1], __fma_rn(A.le[1], g2, g1), A.le[1] * s_e[0] + s_e[2]) : A.le[1] * s_e[0] + s_e[2];   // (explicit: one rounding order in every kernel that holds this body)
+    if (tid == 2) A.acc->e_slot[2] = A.gb_epart ? __fma_rn(A.le[2], __fma_rn(A.le[2], g2, g1), A.le[2] * s_e[0] + s_e[3]) : A.le[2] * s_e[0] + s_e[3];   // (explicit: one rounding order in every kernel that holds this body)
+    if (tid < 6) A.mom_part[(size_t)(n_itiles + 1) * 6 + tid] = tid < 3 ? 0.0 : (A.fgb ? s_e[K2_NE + tid - 3] + gf : s_e[K2_NE + tid - 3]);  // alchemical pair force on the alchemical atoms
 }
 
 __global__ void __launch_bounds__(256) k_finalize(FinArgs A) { finalize_body<false>(A); }

@@ -24,13 +24,18 @@ class NativeEngine:
                               % ", ".join(sorted(k for k in ("custom_pair_mode", "centroid_bonds") if system.extras.get(k))))
         try:
             system.check_custom_forces()
+            system.check_implicit_solvent(integrator)
         except ValueError as e:
             raise EngineError(str(e))
         self._lib = load()
         sd, self._keep_s = system.to_desc()
         idesc, self._keep_i = integrator.to_desc()
         h = C.c_void_p()
-        rc = self._lib.blues_engine_create(C.byref(sd), C.byref(idesc), int(device), C.byref(h))
+        if system.implicit_solvent is not None:
+            gd, self._keep_g = system.implicit_solvent.to_desc()
+            rc = self._lib.blues_engine_create_gb(C.byref(sd), C.byref(idesc), C.byref(gd), int(device), C.byref(h))
+        else:
+            rc = self._lib.blues_engine_create(C.byref(sd), C.byref(idesc), int(device), C.byref(h))
         if rc:
             raise EngineError(self._lib.blues_last_error(None).decode())
         self._h = h

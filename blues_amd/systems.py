@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ._abi import NB_PME, NB_PME_DIRECT, SystemData
+from ._abi import NB_PME, NB_PME_DIRECT, ImplicitSolventData, SystemData
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 _ARRAY_FIELDS = ("box", "mass", "charge", "sigma", "epsilon", "exclusions", "exception_atoms", "exception_params",
@@ -22,12 +22,15 @@ _ARRAY_FIELDS = ("box", "mass", "charge", "sigma", "epsilon", "exclusions", "exc
 _SCALAR_FIELDS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha",
                   "annihilate_electrostatics", "annihilate_sterics", "remove_cm_motion")
 _OPTIONAL_SCALARS = ("pme_order", "dispersion_correction")   # (files written before reciprocal space existed do not have them)
+_GB_FIELDS = ("model", "radius", "scale", "solute_dielectric", "solvent_dielectric", "surface_area_energy")   # SystemData.implicit_solvent, stored as gb_<field>
 
 
 def save_system(path, system: SystemData, **extra):
     d = {k: np.asarray(getattr(system, k)) for k in _ARRAY_FIELDS if getattr(system, k) is not None}
     d.update({k: np.asarray(getattr(system, k)) for k in _SCALAR_FIELDS + _OPTIONAL_SCALARS})
     d["pme_grid"] = np.asarray(system.pme_grid, dtype=np.int32)
+    if system.implicit_solvent is not None:
+        d.update({"gb_" + k: np.asarray(getattr(system.implicit_solvent, k)) for k in _GB_FIELDS})
     d.update({k: np.asarray(v) for k, v in extra.items()})
     np.savez_compressed(path, **d)
 
@@ -43,7 +46,10 @@ def load_system(path):
             kw[k] = z[k].item()
     if "pme_grid" in z.files:
         kw["pme_grid"] = tuple(int(v) for v in z["pme_grid"])
-    extra = {k: z[k] for k in z.files if k not in kw}
+    if "gb_model" in z.files:
+        kw["implicit_solvent"] = ImplicitSolventData(int(z["gb_model"]), z["gb_radius"], z["gb_scale"], float(z["gb_solute_dielectric"]),
+                                                     float(z["gb_solvent_dielectric"]), float(z["gb_surface_area_energy"]))
+    extra = {k: z[k] for k in z.files if k not in kw and not k.startswith("gb_")}
     return SystemData(**kw), extra
 
 
@@ -166,6 +172,7 @@ def tile_system(system: SystemData, reps):
         positions=pos,
         residue_of_atom=None if res is None else np.concatenate([res + c * nres for c in range(ncopy)]).astype(np.int32),
         names=None if system.names is None else list(system.names) * ncopy,
+        implicit_solvent=None if system.implicit_solvent is None else system.implicit_solvent.subset(np.tile(np.arange(n), ncopy)),
     )
 
 
@@ -331,6 +338,15 @@ _FORCE_FIELD_ARRAYS = ("charge", "sigma", "epsilon", "exclusions", "exception_at
 _FORCE_FIELD_SCALARS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha", "pme_order", "dispersion_correction")
 
 
+def same_implicit_solvent(a, b):
+    """Two SystemData.implicit_solvent values describe the same model over the same atoms (both None included)."""
+    if a is None or b is None:
+        return a is None and b is None
+    return (int(a.model) == int(b.model) and float(a.solute_dielectric) == float(b.solute_dielectric) and float(a.solvent_dielectric) == float(b.solvent_dielectric)
+            and float(a.surface_area_energy) == float(b.surface_area_energy) and np.array_equal(np.asarray(a.radius, dtype=np.float64), np.asarray(b.radius, dtype=np.float64))
+            and np.array_equal(np.asarray(a.scale, dtype=np.float64), np.asarray(b.scale, dtype=np.float64)))
+
+
 def alchemical_difference_plan(alchemical: SystemData, plain: SystemData):
     """How D(x) = U_plain(x) - U_alchemical(x; lambda_sterics = lambda_electrostatics = 1) can be had WITHOUT evaluating U_plain, where
     `plain` is the non-alchemical System of the reference's md / alch contexts (blues/simulation.py:791-792) and `alchemical` the NCMC
@@ -355,6 +371,8 @@ def alchemical_difference_plan(alchemical: SystemData, plain: SystemData):
     for name in _FORCE_FIELD_SCALARS:
         if getattr(alchemical, name) != getattr(plain, name):
             return None
+    if not same_implicit_solvent(alchemical.implicit_solvent, plain.implicit_solvent):   # (equal: GB at lambda_electrostatics = 1 is the plain System's)
+        return None
     if alchemical.nonbonded_method != NB_PME:
         return {"kind": "zero"}
     if tuple(alchemical.pme_grid) != tuple(plain.pme_grid) or getattr(alchemical, "barostat", None) or getattr(plain, "barostat", None):

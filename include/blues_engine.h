@@ -177,6 +177,25 @@ typedef struct BluesEngine BluesEngine;
 /* openmm.app.Simulation(topology, system, integrator, platform, properties)
  * (reference blues/simulation.py:730-737).  device = HIP device ordinal. */
 int blues_engine_create(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, int device, BluesEngine **out);
+
+/* Implicit solvent of a BLUES_NB_NOCUTOFF System: OpenMM's GBSAOBCForce (app.OBC1 / app.OBC2) with the ACE surface term, what
+ * createSystem(implicitSolvent=..., soluteDielectric=..., solventDielectric=...) adds (reference blues/simulation.py:139-219).
+ * Additive to ABI 9: neither descriptor above changes.  An alchemical atom's charge and surface term are scaled by
+ * lambda_electrostatics (as openmmtools' AbsoluteAlchemicalFactory treats a GBSAOBCForce: recalled, not source-pinned); Born radii
+ * do not depend on lambda.  Creation fails, with the reason, for a periodic System, null arrays, a radius <= 0.009 nm, a non-positive
+ * dielectric, custom_pair_mode or centroid bonds on the same System, annihilate_electrostatics = 0, and measure_shadow_work /
+ * measure_heat (the ledger's device-side energy sum does not know the GB partials). */
+#define BLUES_GB_NONE 0
+#define BLUES_GB_OBC1 1
+#define BLUES_GB_OBC2 2
+typedef struct BluesImplicitSolventDesc {
+    int32_t model;                       /* BLUES_GB_* */
+    double solute_dielectric, solvent_dielectric;
+    double surface_area_energy;          /* kJ/mol/nm^2; OpenMM's 2.25936; 0 switches the ACE term off */
+    const double *radius, *scale;        /* [n_atoms] nm; dimensionless (prmtop RADII, SCREEN) */
+} BluesImplicitSolventDesc;
+/* gb = NULL (or model BLUES_GB_NONE): blues_engine_create */
+int blues_engine_create_gb(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, const BluesImplicitSolventDesc *gb, int device, BluesEngine **out);
 int blues_engine_destroy(BluesEngine *h);
 const char *blues_last_error(const BluesEngine *h);
 int blues_abi_version(void);
@@ -275,7 +294,8 @@ int blues_mesh_energy(BluesEngine *h, int32_t with_alchemical_charges, double *o
  * [0] bonds [1] angles [2] torsions [3] nonbonded env-env [4] exceptions
  * [5] alchemical sterics [6] alchemical electrostatics [7] restraint
  * [8] Ewald reciprocal space (mesh + self term + erf corrections of excluded pairs + neutralising background)
- * [9] long-range dispersion correction; [8], [9] are 0 unless BLUES_NB_PME */
+ * [9] long-range dispersion correction; [8], [9] are 0 unless BLUES_NB_PME or the engine carries implicit solvent
+ * (blues_engine_create_gb, BLUES_NB_NOCUTOFF only): then [8] is the GB polar energy and [9] the ACE surface term */
 #define BLUES_N_ENERGY_TERMS 10
 int blues_get_energy_terms(BluesEngine *h, double terms[BLUES_N_ENERGY_TERMS]);
 
