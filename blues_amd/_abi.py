@@ -77,6 +77,32 @@ class BluesImplicitSolventDesc(C.Structure):
     ]
 
 
+class BluesMinimizeDesc(C.Structure):
+    """include/blues_engine.h: BluesMinimizeDesc (the constants of the device-resident FIRE minimiser)."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("dt0", C.c_double), ("dt_max", C.c_double), ("f_inc", C.c_double), ("f_dec", C.c_double),
+        ("alpha0", C.c_double), ("f_alpha", C.c_double), ("max_step", C.c_double),
+        ("n_min", C.c_int32),
+    ]
+
+
+class BluesMinimizeResult(C.Structure):
+    _fields_ = [
+        ("converged", C.c_int32), ("iterations", C.c_int32), ("n_pos", C.c_int32), ("pad", C.c_int32),
+        ("fmax", C.c_double), ("dt", C.c_double), ("alpha", C.c_double), ("e_initial", C.c_double), ("e_final", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {"converged": int(self.converged), "iterations": int(self.iterations), "n_pos": int(self.n_pos), "fmax": float(self.fmax),
+                "dt": float(self.dt), "alpha": float(self.alpha), "e_initial": float(self.e_initial), "e_final": float(self.e_final)}
+
+
+MINIMIZE_FIELDS = ("dt0", "dt_max", "f_inc", "f_dec", "alpha0", "f_alpha", "max_step", "n_min")
+# additive entry points (BLUES_ABI_VERSION unchanged): a library built before them loads, and the wrappers that need them say so
+OPTIONAL_SYMBOLS = ("blues_minimize_default", "blues_minimize", "blues_batch_minimize")
+
+
 class BluesTuning(C.Structure):
     """include/blues_engine.h: BluesTuning (launch-policy overrides; the library reads no environment variables)."""
     _fields_ = [
@@ -410,8 +436,13 @@ def declare_engine_prototypes(lib):
         "blues_debug_check_guards": ([C.POINTER(C.c_int64)], C.c_int),
         "blues_batch_kernel_timing": ([H, C.c_int32], C.c_int),
         "blues_batch_get_kernel_timing": ([H, _dp], C.c_int),
+        "blues_minimize_default": ([C.POINTER(BluesMinimizeDesc)], None),
+        "blues_minimize": ([H, C.c_double, C.c_int32, C.POINTER(BluesMinimizeDesc), C.POINTER(BluesMinimizeResult)], C.c_int),
+        "blues_batch_minimize": ([H, C.c_double, C.c_int32, C.POINTER(BluesMinimizeDesc), C.POINTER(C.c_int32), C.POINTER(BluesMinimizeResult), C.POINTER(C.c_int32)], C.c_int),
     }
     for name, (args, res) in protos.items():
+        if name in OPTIONAL_SYMBOLS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.argtypes = args
         fn.restype = res
@@ -432,4 +463,5 @@ ENGINE_SYMBOLS = (
     "blues_batch_set_velocities_to_temperature", "blues_batch_mesh_energy",
     "blues_batch_get_stats", "blues_batch_get_counters", "blues_batch_time_nonbonded", "blues_batch_time_nonbonded_modes",
     "blues_batch_kernel_timing", "blues_batch_get_kernel_timing", "blues_debug_setup_seconds", "blues_debug_check_guards",
+    "blues_minimize_default", "blues_minimize", "blues_batch_minimize",
 )

@@ -259,6 +259,21 @@ class Context(object):
         return self._system
 
 
+def _force_tolerance(tolerance):
+    """A force tolerance as a number of kJ/mol/nm (a Quantity is converted)."""
+    return unit.value_in(tolerance, "kilojoule/(nanometer*mole)") if isinstance(tolerance, unit.Quantity) else float(tolerance)
+
+
+class LocalEnergyMinimizer(object):
+    """openmm.LocalEnergyMinimizer stand-in: minimize(context, tolerance, maxIterations) moves the Context's positions to a local
+    minimum of the potential energy under its constraints -- on the device (NativeEngine.minimize: FIRE)."""
+
+    @staticmethod
+    def minimize(context, tolerance=10, maxIterations=0):
+        """tolerance: kJ/mol/nm or a Quantity; maxIterations 0: the engine's default (10000).  Returns the engine's result dict."""
+        return context._engine.minimize(_force_tolerance(tolerance), int(maxIterations))
+
+
 class Simulation(object):
     """openmm.app.Simulation stand-in (reference blues/simulation.py:732-737): `context` is read AND
     assigned by BLUES (simulation.py:1037,1070,1079,1086); reporters follow the OpenMM protocol
@@ -285,14 +300,21 @@ class Simulation(object):
             self.barostat = MonteCarloBarostat(p_bar, temp, freq, seed=getattr(integrator, "_seed", 0) + 7919 * (replica + 1))
             self._barostat_count = 0
 
-    def minimizeEnergy(self, tolerance=10.0, maxIterations=0):
+    def minimizeEnergy(self, tolerance=10.0, maxIterations=0, method="host"):
         """app.Simulation.minimizeEnergy (the reference calls it in its test fixtures only, blues/tests/test_simulation.py:139-141).
-        OpenMM runs L-BFGS; here: steepest descent on the engine's forces with an adaptive step -- accepted while the potential
-        energy falls, halved otherwise -- and the constraints re-imposed after every displacement (the procedure of the oracle's
-        orc_minimize).  tolerance: largest force component (kJ/mol/nm) at which to stop; maxIterations 0: up to 500."""
+        OpenMM runs L-BFGS; here, method="host": steepest descent on the engine's forces with an adaptive step -- accepted while the
+        potential energy falls, halved otherwise -- and the constraints re-imposed after every displacement (the procedure of the
+        oracle's orc_minimize).  tolerance: largest force component (kJ/mol/nm) at which to stop; maxIterations 0: up to 500.
+        method="device": the device-resident FIRE minimiser (LocalEnergyMinimizer.minimize), whose iterations stay on
+        the GPU and whose convergence test uses the constraint-projected force; it returns the engine's result dict.  The default
+        stays "host" so that nothing that exists changes behaviour; flipping it is the follow-up."""
+        if method == "device":
+            return LocalEnergyMinimizer.minimize(self.context, tolerance, maxIterations)
+        if method != "host":
+            raise ValueError("minimizeEnergy: method %r (\"host\" or \"device\")" % (method,))
         e = self.context._engine
         s = self.system
-        tol = unit.value_in(tolerance, "kilojoule/(nanometer*mole)") if isinstance(tolerance, unit.Quantity) else float(tolerance)
+        tol = _force_tolerance(tolerance)
         mobile = np.asarray(s.mass) > 0
         ca = np.asarray(getattr(s, "constraint_atoms", []), dtype=np.int64).reshape(-1, 2)
         cd = np.asarray(getattr(s, "constraint_dist", []), dtype=np.float64).reshape(-1)

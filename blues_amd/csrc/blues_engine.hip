@@ -40,6 +40,7 @@
 #include "kernels_batch.h"
 #include "kernels_nocutoff.h"
 #include "kernels_gb.h"
+#include "kernels_minimize.h"
 static_assert(CENT_GROUP == BLUES_MAX_CENTROID_GROUP, "a centroid-bond term has one place per atom the C-ABI allows in a group (kernels_bonded.h, build_bonded)");
 static_assert(T_CENT >= T_NTYPES, "T_CENT is an entry type only: it has no slot in the per-type arrays");
 
@@ -290,6 +291,10 @@ struct BluesEngine {
     // implicit solvent (kernels_gb.h, NoCutoff only): model (BLUES_GB_*; 0: none), its constants, per-atom parameters and the three passes' buffers (nocut_layout)
     int gb_model = 0, gb_blocks = 0; double gb_pref = 0.0, gb_sa = 0.0, gb_eps_in = 1.0, gb_eps_out = 78.5, gb_sa_energy = 0.0; std::vector<double> gb_radius, gb_scale;
     DBuf<GbArgs> d_gb_rec; long long gb_rec_epoch = -1;   // a lone engine's own record for the kernels (launch_gb)
+    // the device-resident minimiser (kernels_minimize.h): its own velocities, the blocks' partials, the double-buffered state;
+    // the record a lone launch reads (fire_rec_epoch / fire_rec_req: what it was made for) and the settings of the running call
+    DBuf<double> d_fire_v, d_fire_part; DBuf<FireState> d_fire_state; DBuf<FireRec> d_fire_rec; long long fire_rec_epoch = -1; const int* fire_rec_req = nullptr;
+    int fire_parity = 0; FireRec fire_cfg;
     DBuf<double4> d_gbpar; DBuf<int> d_gb_alch; DBuf<double> d_gb_born, d_gb_G, d_gb_fdir, d_fgb, d_gb_epart;
     DBuf<double4> d_ncpar; int nc_blocks_f = 0, nc_blocks_e = 0;   // NoCutoff: per-atom parameters, blocks of the force / energy launches (nocut_layout)
     // fragment lists (every environment atom mobile): the static cut of the environment into fragments of <= 3 atoms
@@ -416,6 +421,8 @@ struct BluesBatch {
     bool defer_work = false; std::vector<DevAccum*> h_wacc; std::vector<double> h_wdelta; DBuf<DevAccum*> d_wacc; DBuf<double> d_wdelta;   // add_work of all members in one launch
     DBuf<GbArgs> d_gb;   // NoCutoff members with implicit solvent: the records of kernels_gb.h (batch_refresh_args)
     DBuf<NcArgs> d_nc;   // NoCutoff members: the records of the all-pairs kernel (batch_refresh_args)
+    DBuf<FireState*> d_fire_ptrs; DBuf<FireState> d_fire_out;
+    DBuf<FireRec> d_fire; std::vector<uint64_t> fire_epoch; std::vector<char> fire_active;   // the minimiser's records (launch_fire) and what they were made from
     std::vector<EvPair> k1t_pairs; int k1t_every = 0; int64_t k1t_seen = 0, k1t_n = 0; double k1t_sum_us = 0.0, k1t_max_us = 0.0;
     int R() const { return (int)eng.size(); }
 };
@@ -3939,12 +3946,11 @@ int blues_get_box(BluesEngine* h, double box[9]) {
     return 0;
 }
 
-int blues_get_forces(BluesEngine* h, double* out, int32_t n_atoms) {
-    if (n_atoms != h->n) E_FAIL(h, "expected %d atoms, got %d", h->n, n_atoms);
-    HIP_OK(h, hipSetDevice(h->device));
+// forces at the current alchemical parameters: a pass whose slot 0 carries them, with the sums of its own (blues_get_forces, and
+// every iteration of the minimiser)
+static int current_force_pass(BluesEngine* h) {
     if (flush_program(h)) return 1;
     h->fin_pending = false;   // (this call runs a pass and the sums of its own)
-    // forces at the current alchemical parameters: evaluate a pass whose slot 0 carries them
     if (ensure_sorted(h)) return 1;
     double ls[3] = {h->cur_ls, h->cur_ls, h->cur_ls}, le[3] = {h->cur_le, h->cur_le, h->cur_le};
     int rc = launch_lists_p(h, h->lists_forced);
@@ -3956,7 +3962,13 @@ int blues_get_forces(BluesEngine* h, double* out, int32_t n_atoms) {
     if (rc) return 1;
     if (launch_pme(h, 0)) return 1;
     if (h->gb_model && launch_gb_p<false>(h, le)) return 1;
-    if (launch_bonded_and_finalize(h, le, false)) return 1;
+    return launch_bonded_and_finalize(h, le, false);
+}
+
+int blues_get_forces(BluesEngine* h, double* out, int32_t n_atoms) {
+    if (n_atoms != h->n) E_FAIL(h, "expected %d atoms, got %d", h->n, n_atoms);
+    HIP_OK(h, hipSetDevice(h->device));
+    if (current_force_pass(h)) return 1;
     IntArgs A = make_int_args(h);
     DBuf<double> tmp;
     try { tmp.alloc((size_t)3 * h->n); } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
@@ -3980,6 +3992,127 @@ int blues_set_velocities_to_temperature(BluesEngine* h, double temperature, uint
     // (no read-back here: a velocity-constraint failure stays flagged on the device and is raised by the next step, which
     // checks the flags anyway -- a synchronous check per chain was 20 us of host time for each of R chains per iteration)
     return flush_program(h);
+}
+
+// ---- the device-resident minimiser (kernels_minimize.h): FIRE on the constraint manifold.  One iteration = the force
+// pass of blues_get_forces + k_fire_reduce_b + k_fire_step_b; a member that is done is inert on the device, so the result does not depend
+// on how often the host looks (FIRE_POLL).  Nothing of the protocol is touched: h_step, lambdas, protocol work, work trace, noise and
+// draw counters, the energy ledger.
+#define FIRE_POLL 16
+void blues_minimize_default(BluesMinimizeDesc* d) {
+    if (!d) return;
+    memset(d, 0, sizeof *d);
+    d->struct_size = (int32_t)sizeof(BluesMinimizeDesc);
+    d->dt0 = 0.001; d->dt_max = 0.01; d->f_inc = 1.1; d->f_dec = 0.5; d->alpha0 = 0.1; d->f_alpha = 0.99; d->max_step = 0.01; d->n_min = 5;
+}
+// what the call refuses, with the reason in the engine's error
+static int minimize_refuse(BluesEngine* h, double tolerance, int max_iterations, const BluesMinimizeDesc* d) {
+    if (!(tolerance > 0.0)) E_FAIL(h, "blues_minimize: tolerance %g kJ/mol/nm must be positive", tolerance);
+    if (max_iterations < 0) E_FAIL(h, "blues_minimize: max_iterations %d is negative (0: the default of 10000)", max_iterations);
+    if (h->n_gen()) E_FAIL(h, "blues_minimize: the engine carries general clusters of constraints (AllBonds / HAngles): their solver is not part of the minimiser's kernels");
+    if (!h->have_positions) E_FAIL(h, "positions have not been set");
+    if (d) {
+        if (d->struct_size != (int32_t)sizeof(BluesMinimizeDesc)) E_FAIL(h, "blues_minimize: BluesMinimizeDesc of %d bytes, this library expects %d (use blues_minimize_default)", d->struct_size, (int)sizeof(BluesMinimizeDesc));
+        if (!(d->dt0 > 0.0) || !(d->dt_max >= d->dt0) || !(d->f_inc >= 1.0) || !(d->f_dec > 0.0 && d->f_dec < 1.0) || !(d->alpha0 > 0.0 && d->alpha0 < 1.0) || !(d->f_alpha > 0.0 && d->f_alpha <= 1.0) || !(d->max_step > 0.0) || d->n_min < 0)
+            E_FAIL(h, "blues_minimize: the descriptor's constants are out of range (dt0 > 0, dt_max >= dt0, f_inc >= 1, 0 < f_dec < 1, 0 < alpha0 < 1, 0 < f_alpha <= 1, max_step > 0, n_min >= 0)");
+    }
+    return 0;
+}
+// every call starts fresh: vmin = 0, dt = dt0, both halves of the state record
+static int fire_begin(BluesEngine* h, double tolerance, int max_iterations, const BluesMinimizeDesc* d) {
+    BluesMinimizeDesc def; blues_minimize_default(&def);
+    if (!d) d = &def;
+    FireRec& c = h->fire_cfg; memset(&c, 0, sizeof c);
+    c.active = 1; c.max_iter = max_iterations ? max_iterations : 10000; c.n_min = d->n_min;
+    c.tol_f = tolerance; c.dt_max = d->dt_max; c.f_inc = d->f_inc; c.f_dec = d->f_dec; c.alpha0 = d->alpha0; c.f_alpha = d->f_alpha; c.max_step = d->max_step;
+    FireState S; memset(&S, 0, sizeof S); S.dt = d->dt0; S.alpha = d->alpha0;
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    try { h->d_fire_v.alloc((size_t)3 * h->n); h->d_fire_part.alloc((size_t)4 * std::max(1, h->int_blocks)); h->d_fire_state.upload(std::vector<FireState>(2, S)); } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+    h->fire_parity = 0; h->fire_rec_epoch = -1;
+    return 0;
+}
+static FireRec make_fire_rec(BluesEngine* h) {
+    FireRec r = h->fire_cfg;
+    r.vmin = h->d_fire_v.p; r.part = h->d_fire_part.p; r.state = h->d_fire_state.p; r.in = make_int_args(h);
+    return r;
+}
+// the two kernels of an iteration; a batch's leader covers the members in lock step (their records: B->d_fire)
+static int launch_fire(BluesEngine* h) {
+    if ((size_t)4 * h->int_blocks > h->d_fire_part.n || !h->d_fire_state.p) E_FAIL(h, "internal: the minimiser's buffers were not prepared for this layout");
+    const dim3 block(h->int_threads);
+    if (batch_lead(h)) {
+        BluesBatch* B = h->batch; const int R = B->R();
+        bool dirty = (int)B->fire_epoch.size() != R;
+        if (dirty) { B->fire_epoch.assign(R, 0); B->fire_active.assign(R, 0); }
+        for (int r = 0; r < R; r++) dirty |= B->fire_epoch[r] != B->eng[r]->args_epoch || B->fire_active[r] != B->rec_active[r];
+        if (dirty) {
+            std::vector<FireRec> recs(R);
+            for (int r = 0; r < R; r++) {
+                BluesEngine* m = B->eng[r];
+                if (B->rec_active[r] && m->sorted_ok && m->d_fire_state.p && (size_t)4 * m->int_blocks <= m->d_fire_part.n) recs[r] = make_fire_rec(m);
+                else memset(&recs[r], 0, sizeof(FireRec));
+                B->fire_epoch[r] = m->args_epoch; B->fire_active[r] = B->rec_active[r];
+            }
+            HIP_OK(h, hipStreamSynchronize(h->cur));   // (the records may be in use by launches still in flight)
+            try { B->d_fire.upload(recs); } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+        }
+        const dim3 grid(h->int_blocks, R);
+        hipLaunchKernelGGL(k_fire_reduce_b, grid, block, 0, h->cur, B->d_fire.p, h->fire_parity);
+        hipLaunchKernelGGL(k_fire_step_b, grid, block, 0, h->cur, B->d_fire.p, h->fire_parity);
+    } else if (!batch_dry(h)) {
+        if (h->fire_rec_epoch != (long long)h->args_epoch || h->fire_rec_req != batch_req_ptr(h)) {
+            std::vector<FireRec> rec(1, make_fire_rec(h));
+            HIP_OK(h, hipStreamSynchronize(h->cur));
+            try { h->d_fire_rec.upload(rec); } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+            h->fire_rec_epoch = (long long)h->args_epoch; h->fire_rec_req = batch_req_ptr(h);
+        }
+        const dim3 grid(h->int_blocks, 1);
+        hipLaunchKernelGGL(k_fire_reduce_b, grid, block, 0, h->cur, h->d_fire_rec.p, h->fire_parity);
+        hipLaunchKernelGGL(k_fire_step_b, grid, block, 0, h->cur, h->d_fire_rec.p, h->fire_parity);
+    }
+    h->fire_parity ^= 1;
+    h->st_launches += 2;
+    h->ecache.clear(); h->pass_valid = false;   // the launch may move atoms
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+static int minimize_body(BluesEngine* h) { return current_force_pass(h) || launch_fire(h); }
+static int minimize_prep(BluesEngine* h) { if (flush_program(h) || emit(h, OP_PREP)) return 1; return 0; }   // (flushed by the caller: in lock step for a batch)
+// afterwards: the velocity constraints on the engine's real velocities at the new positions (queued; the caller flushes), and what a
+// change of positions invalidates
+static int minimize_after(BluesEngine* h) {
+    h->ecache.clear(); h->pass_valid = false; h->fin_pending = false; h->ke_cache_valid = false;
+    return emit(h, OP_RATTLE);
+}
+static void minimize_result(const FireState& S, double e0, double e1, BluesMinimizeResult* out) {
+    memset(out, 0, sizeof *out);
+    out->converged = S.converged; out->iterations = S.iter; out->n_pos = S.n_pos; out->fmax = S.fmax; out->dt = S.dt; out->alpha = S.alpha; out->e_initial = e0; out->e_final = e1;
+}
+
+int blues_minimize(BluesEngine* h, double tolerance, int32_t max_iterations, const BluesMinimizeDesc* d, BluesMinimizeResult* out) {
+    if (!h) return 2;
+    HIP_OK(h, hipSetDevice(h->device));
+    if (minimize_refuse(h, tolerance, max_iterations, d)) return 1;
+    if (h->batch && h->batch->entered) E_FAIL(h, "blues_minimize: the engine's batch is inside a batched call");
+    if (ensure_sorted(h) || minimize_prep(h) || flush_program(h)) return 1;
+    h->pass_valid = false;
+    double e0 = 0.0, e1 = 0.0;
+    if (check_flags(h) || total_energy(h, &e0)) return 1;
+    if (fire_begin(h, tolerance, max_iterations, d)) return 1;
+    FireState S; memset(&S, 0, sizeof S);
+    for (int it = 0;; it++) {
+        if (it > 0 && it % FIRE_POLL == 0) {
+            if (check_flags(h)) return 1;   // (synchronises)
+            HIP_OK(h, hipMemcpy(&S, h->d_fire_state.p + h->fire_parity, sizeof S, hipMemcpyDeviceToHost));
+            if (S.done) break;
+            if (it % RESORT_POLL == 0 && !nocut(h) && poll_resort(h)) return 1;
+        }
+        if (minimize_body(h)) return 1;
+    }
+    if (minimize_after(h) || flush_program(h) || check_flags(h)) return 1;
+    if (total_energy(h, &e1)) return 1;
+    if (out) minimize_result(S, e0, e1, out);
+    return 0;
 }
 
 int blues_get_energy(BluesEngine* h, double* potential, double* kinetic) {
@@ -4823,6 +4956,86 @@ int blues_batch_set_velocities_to_temperature(BluesBatch* B, double temperature,
     B->active = saved_active; B->leader = B->eng[0];
     batch_leave(B);
     return rc;
+}
+
+// blues_minimize of every member in the mask (NULL: all) as one launch sequence: the members in the batch's layout advance in lock step
+// (batch_phase), a member that has converged stays in the launches and is inert on the device; the call runs until every member is
+// converged or out of iterations.  status[r] != 0: member r raised (blues_last_error of its engine); out[r] is zeroed for it.
+int blues_batch_minimize(BluesBatch* B, double tolerance, int32_t max_iterations, const BluesMinimizeDesc* d, const int32_t* mask, BluesMinimizeResult* out, int32_t* status) {
+    if (!B || B->eng.empty()) { if (B) B->err = "the batch has been dissolved (one of its engines was destroyed)"; return 2; }
+    if (!out) { B->err = "blues_batch_minimize: null result array"; return 2; }
+    if (hipSetDevice(B->eng[0]->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
+    const int R = B->R();
+    std::vector<int> st(R, 0);
+    std::vector<char> saved_active = B->active;
+    B->failed.assign(R, 0);
+    for (int r = 0; r < R; r++) { memset(&out[r], 0, sizeof out[r]); B->active[r] = (!mask || mask[r]) ? 1 : 0; if (!B->active[r]) B->failed[r] = 1; }
+    auto leave = [&](int rc) {
+        B->active = saved_active; B->leader = B->eng[0];
+        batch_leave(B);
+        if (status) for (int r = 0; r < R; r++) status[r] = st[r];
+        return rc;
+    };
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && minimize_refuse(B->eng[r], tolerance, max_iterations, d)) member_fail(B, st.data(), r);
+    if (batch_enter(B)) return leave(1);
+    for (int r = 0; r < R; r++) if (member_stepping(B, r)) { B->eng[r]->tracing = false; if (ensure_sorted(B->eng[r]) || minimize_prep(B->eng[r])) member_fail(B, st.data(), r); }
+    if (!batch_pick_leader(B)) return leave(0);
+    if (B->leader) for (int r = 0; r < R; r++) if (member_shared(B, r)) {
+        const char* why = "";
+        if (!batch_congruent_cached(B, r, B->leader, &why)) { B->err = std::string("replicas of a batch must be congruent; they differ in ") + why; return leave(1); }
+        if (B->eng[r]->cur_ls != B->leader->cur_ls || B->eng[r]->cur_le != B->leader->cur_le) { B->err = "blues_batch_minimize: the members stand at different alchemical parameters (their force passes cannot share launches)"; return leave(1); }
+    }
+    if (batch_refresh_args(B) || batch_phase(B, st.data(), flush_program)) return leave(1);   // the first-step constraints (OP_PREP)
+    for (int r = 0; r < R; r++) if (member_stepping(B, r)) B->eng[r]->pass_valid = false;
+    std::vector<double> e0(R, 0.0), e1(R, 0.0);
+    if (batch_prefetch(B, 1)) return leave(1);
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && (total_energy(B->eng[r], &e0[r]) || fire_begin(B->eng[r], tolerance, max_iterations, d))) member_fail(B, st.data(), r);
+    B->fire_epoch.clear();
+    std::vector<FireState> S(R); std::vector<FireState*> ptrs(R, nullptr);
+    for (int r = 0; r < R; r++) { memset(&S[r], 0, sizeof(FireState)); if (member_stepping(B, r)) ptrs[r] = B->eng[r]->d_fire_state.p; }
+    try { B->d_fire_ptrs.upload(ptrs); B->d_fire_out.reserve(R); } catch (std::string& e) { B->err = e; return leave(1); }
+    auto read_states = [&](int parity) {   // one gather, one read-back (after the caller's launches; synchronises)
+        hipLaunchKernelGGL(k_fire_gather_b, dim3((R + 255) / 256), dim3(256), 0, B->stream, B->d_fire_ptrs.p, R, parity, B->d_fire_out.p);
+        if (hipStreamSynchronize(B->stream) != hipSuccess) return 1;
+        std::vector<FireState> got;
+        try { B->d_fire_out.download(got); } catch (std::string&) { return 1; }
+        for (int r = 0; r < R; r++) if (member_stepping(B, r)) S[r] = got[r];
+        return 0;
+    };
+    auto parity_now = [&]() { for (int r = 0; r < R; r++) if (member_stepping(B, r)) return B->eng[r]->fire_parity; return 0; };
+    for (int it = 0;; it++) {
+        if (it > 0 && it % FIRE_POLL == 0) {
+            if (!batch_pick_leader(B)) break;
+            if (batch_refresh_args(B)) return leave(1);
+            std::vector<int> hints;
+            try { batch_launch_hints(B); if (read_states(parity_now())) { B->err = "stream synchronisation failed"; return leave(1); } batch_read_hints(B, hints); } catch (std::string& e) { B->err = e; return leave(1); }
+            for (int r = 0; r < R; r++) if (member_stepping(B, r) && ((hints[r] & 2) || B->eng[r]->straggler || !B->rec_active[r]) && check_flags(B->eng[r])) member_fail(B, st.data(), r);
+            bool all_done = true;
+            for (int r = 0; r < R; r++) if (member_stepping(B, r)) all_done &= S[r].done != 0;
+            if (all_done) break;
+            if (it % RESORT_POLL == 0 && !nocut(B->eng[0])) {   // the re-sort poll of the members still at work, as the lone loop's
+                std::vector<BluesEngine*> todo;
+                for (int r = 0; r < R; r++) if (member_stepping(B, r) && !S[r].done && (resort_by_age(B->eng[r]) || (hints[r] & 1) || B->eng[r]->straggler || !B->rec_active[r])) {
+                    const int want = resort_wanted(B->eng[r]);
+                    if (want < 0) member_fail(B, st.data(), r); else if (want) todo.push_back(B->eng[r]);
+                }
+                if (!todo.empty()) {
+                    relayout_many(todo, [](BluesEngine*) { return true; });
+                    for (BluesEngine* m : todo) if (m->relayout_failed) member_fail(B, st.data(), m->batch_index);
+                    B->st_poll_resorts += (int64_t)todo.size();
+                }
+                if (batch_poll_reshape(B, st.data())) return leave(1);
+            }
+        }
+        if (batch_phase(B, st.data(), minimize_body)) return leave(1);
+    }
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && minimize_after(B->eng[r])) member_fail(B, st.data(), r);
+    if (batch_phase(B, st.data(), flush_program)) return leave(1);
+    if (read_states(parity_now())) { B->err = "stream synchronisation failed"; return leave(1); }
+    for (int r = 0; r < R; r++) if (member_stepping(B, r) && check_flags(B->eng[r])) member_fail(B, st.data(), r);
+    if (batch_prefetch(B, 1)) return leave(1);
+    for (int r = 0; r < R; r++) if (member_stepping(B, r)) { if (total_energy(B->eng[r], &e1[r])) member_fail(B, st.data(), r); else minimize_result(S[r], e0[r], e1[r], &out[r]); }
+    return leave(0);
 }
 
 // In-situ timing of the nonbonded force kernel: `every` > 0 brackets every `every`-th lock-step force launch of the stepping

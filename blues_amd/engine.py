@@ -127,6 +127,17 @@ class NativeEngine:
     def set_velocities_to_temperature(self, T, seed=0):
         self._check(self._lib.blues_set_velocities_to_temperature(self._h, float(T), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
+    def minimize(self, tolerance=10.0, max_iterations=0, **fire):
+        """Energy minimisation on the device (include/blues_engine.h: blues_minimize): FIRE under the engine's constraints until the
+        largest component of the constraint-projected force is <= tolerance (kJ/mol/nm) or max_iterations (0: 10000) are spent.
+        fire: fields of BluesMinimizeDesc (dt0, dt_max, f_inc, f_dec, alpha0, f_alpha, max_step, n_min).  Returns the result record
+        as a dict: converged, iterations, n_pos, fmax, dt, alpha, e_initial, e_final."""
+        desc = _minimize_desc(self._lib, fire)
+        out = _abi.BluesMinimizeResult()
+        self.__dict__["_gcache"] = {}
+        self._check(self._lib.blues_minimize(self._h, float(tolerance), int(max_iterations), desc, C.byref(out)))
+        return out.as_dict()
+
     def energies(self):
         """(potential, kinetic) in one call (state.getPotentialEnergy / getKineticEnergy of one getState)."""
         e = C.c_double(); k = C.c_double(); self._check(self._lib.blues_get_energy(self._h, C.byref(e), C.byref(k))); return e.value, k.value
@@ -199,6 +210,24 @@ class NativeEngine:
     def audit_lists(self):
         """(pairs within the cutoff, pairs missing from the lists the nonbonded kernel would walk now) -- include/blues_engine.h: blues_audit_lists."""
         out = (C.c_int64 * 2)(); self._check(self._lib.blues_audit_lists(self._h, out)); return int(out[0]), int(out[1])
+
+
+def _minimize_desc(lib, fire):
+    """BluesMinimizeDesc from keyword overrides (None: the library's defaults); EngineError when the library has no minimiser."""
+    missing = [name for name in _abi.OPTIONAL_SYMBOLS if not hasattr(lib, name)]
+    if missing:
+        raise EngineError("the engine library lacks %s: it was built before the device-resident minimiser; rebuild it "
+                          "(python -m blues_amd.build)" % ", ".join(missing))
+    unknown = sorted(set(fire) - set(_abi.MINIMIZE_FIELDS))
+    if unknown:
+        raise EngineError("minimize: unknown setting %s (known: %s)" % (", ".join(unknown), ", ".join(_abi.MINIMIZE_FIELDS)))
+    if not fire:
+        return None
+    d = _abi.BluesMinimizeDesc()
+    lib.blues_minimize_default(C.byref(d))
+    for k, v in fire.items():
+        setattr(d, k, int(v) if k == "n_min" else float(v))
+    return d
 
 
 class DeviceSnapshot:
@@ -377,6 +406,32 @@ class NativeBatch:
         sd = (C.c_uint64 * R)(*[int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds])
         if self._lib.blues_batch_set_velocities_to_temperature(self._h, float(temperature), sd, self._mask(active)):
             self._fail()
+
+    def minimize_all(self, tolerance=10.0, max_iterations=0, active=None, raise_errors=True, **fire):
+        """NativeEngine.minimize of every member (or of those with active[r] true) as one launch sequence (blues_batch_minimize).
+        Returns (errors, results): errors[r] is None or the EngineError member r raised (with raise_errors the first is raised),
+        results[r] the member's result dict (None for a member that sat out or raised)."""
+        R = len(self.engines)
+        desc = _minimize_desc(self._lib, fire)
+        out = (_abi.BluesMinimizeResult * R)()
+        status = (C.c_int32 * R)()
+        for r, e in enumerate(self.engines):
+            if active is None or active[r]:
+                e.__dict__["_gcache"] = {}
+        if self.device_turn is not None:
+            with self.device_turn:
+                rc = self._lib.blues_batch_minimize(self._h, float(tolerance), int(max_iterations), desc, self._mask(active), out, status)
+        else:
+            rc = self._lib.blues_batch_minimize(self._h, float(tolerance), int(max_iterations), desc, self._mask(active), out, status)
+        if rc:
+            self._fail()
+        errors = [EngineError(self._lib.blues_last_error(e._h).decode()) if status[r] else None for r, e in enumerate(self.engines)]
+        if raise_errors:
+            for err in errors:
+                if err is not None:
+                    raise err
+        results = [out[r].as_dict() if (errors[r] is None and (active is None or active[r])) else None for r in range(R)]
+        return errors, results
 
     def mesh_energy_all(self, with_alchemical_charges=False, active=None):
         """(R,) reciprocal-space mesh energies of the members' current coordinates: one launch, one read-back (blues_batch_mesh_energy)."""

@@ -393,6 +393,22 @@ class BatchedBLUESSimulation(object):
             if b is not None:
                 b.close()
 
+    def minimize(self, which="md", tolerance=10, maxIterations=0):
+        """Simulation.minimizeEnergy(method="device") of every chain's Simulation of one kind ("md", "ncmc" or "alch"): where the chains
+        share a native batch, one minimize_all (one launch sequence for all chains); chain by chain otherwise.  Returns the chains'
+        result dicts (None for a retired chain)."""
+        from .context import _force_tolerance
+        batch = {"md": self._md_batch, "ncmc": self._ncmc_batch, "alch": self._alch_batch}.get(which)
+        sims = [getattr(c, "_%s_sim" % which, None) for c in self.chains]
+        if which not in ("md", "ncmc", "alch") or any(s_ is None for s_ in sims):
+            raise ValueError("minimize: the chains have no %r Simulation" % (which,))
+        tol = _force_tolerance(tolerance)
+        alive = self._alive()
+        if batch is not None:
+            _, results = batch.minimize_all(tol, int(maxIterations), active=alive)
+            return results
+        return [sims[r].minimizeEnergy(tol, maxIterations, method="device") if alive[r] else None for r in range(len(sims))]
+
     def for_each_chain(self, fn, indices=None):
         """[fn(r, chain) for the given chains] -- on the pool when there is one."""
         idx = list(range(len(self.chains))) if indices is None else list(indices)

@@ -276,6 +276,30 @@ int blues_get_forces(BluesEngine *h, double *xyz_kj_per_mol_nm, int32_t n_atoms)
 int blues_get_box(BluesEngine *h, double box[9]);
 /* context.setVelocitiesToTemperature(T) (simulation.py:743, 1187) */
 int blues_set_velocities_to_temperature(BluesEngine *h, double temperature, uint64_t seed);
+
+/* LocalEnergyMinimizer.minimize / Simulation.minimizeEnergy on the device: FIRE (Bitzek et al., PRL 97, 170201) on the constraint
+ * manifold with the engine's own SHAKE / RATTLE, all of it fp64 but the force pass.  One iteration is the force pass of
+ * blues_get_forces (the context's current lambdas) and two small kernels; nothing is copied to the host but a 40-byte state record
+ * every 16 iterations.  Converged: the largest component of the force with its parts along the constraints removed is <= tolerance
+ * (kJ/mol/nm) over the mobile atoms.  Reaching max_iterations is not an error (converged = 0).  Every call starts fresh.  Afterwards
+ * the velocity constraints are re-imposed on the engine's velocities at the new positions; step counter, lambdas, protocol work, work
+ * trace, noise and the energy ledger are untouched.  Refused: an engine with general constraint clusters (AllBonds / HAngles),
+ * tolerance <= 0, max_iterations < 0. */
+typedef struct BluesMinimizeDesc {
+    int32_t struct_size;       /* sizeof(BluesMinimizeDesc) of the caller: set by blues_minimize_default */
+    double dt0, dt_max;        /* ps: first and largest time step (0.001, 0.01) */
+    double f_inc, f_dec;       /* growth / cut of the time step (1.1, 0.5) */
+    double alpha0, f_alpha;    /* mixing parameter and its decay (0.1, 0.99) */
+    double max_step;           /* nm: no atom is displaced further per iteration before the constraints (0.01) */
+    int32_t n_min;             /* downhill iterations before the time step grows (5) */
+} BluesMinimizeDesc;
+typedef struct BluesMinimizeResult {
+    int32_t converged, iterations, n_pos, pad;
+    double fmax, dt, alpha;    /* projected fmax at the final positions; the state FIRE ended in */
+    double e_initial, e_final; /* potential energy (kJ/mol) after the initial constraint step / at the end */
+} BluesMinimizeResult;
+void blues_minimize_default(BluesMinimizeDesc *d);
+int blues_minimize(BluesEngine *h, double tolerance, int32_t max_iterations /* 0: 10000 */, const BluesMinimizeDesc *d /* NULL: defaults */, BluesMinimizeResult *out);
 /* state.getPotentialEnergy() / getKineticEnergy() (simulation.py:908-909) */
 int blues_get_energy(BluesEngine *h, double *potential, double *kinetic);
 /* The potential energy of the current coordinates with lambda_sterics / lambda_electrostatics set to the given values, the
@@ -437,6 +461,10 @@ int blues_batch_read_atoms(BluesBatch *b, BluesSnapshot *const *snaps /* NULL: t
 int blues_batch_reset(BluesBatch *b, const int32_t *mask);                                                       /* blues_reset */
 int blues_batch_set_velocities_to_temperature(BluesBatch *b, double temperature, const uint64_t *seeds,
                                               const int32_t *mask);                                              /* blues_set_velocities_to_temperature */
+/* blues_minimize of the members in the mask as one launch sequence; a member that is done stays inert in the launches of the others,
+ * and every member's result and positions are bitwise those of the same engine minimised alone.  status[r] != 0: member r raised. */
+int blues_batch_minimize(BluesBatch *b, double tolerance, int32_t max_iterations, const BluesMinimizeDesc *d, const int32_t *mask,
+                         BluesMinimizeResult *out /* [count] */, int32_t *status /* [count] or NULL */);
 int blues_batch_mesh_energy(BluesBatch *b, int32_t with_alchemical_charges, const int32_t *mask, double *out /* [count] */);   /* blues_mesh_energy */
 
 /* [0] steps issued in lock step (one launch for all members) [1] steps that
