@@ -77,6 +77,22 @@ class BluesImplicitSolventDesc(C.Structure):
     ]
 
 
+class BluesSystemExt(C.Structure):
+    """include/blues_engine.h: BluesSystemExt (additive System options; blues_engine_create_ext)."""
+    _fields_ = [("struct_size", C.c_int32), ("alchemical_pme_treatment", C.c_int32)]
+
+
+# SystemData.alchemical_pme_treatment -> BluesSystemExt.alchemical_pme_treatment (BLUES_ALCH_PME_*)
+ALCHEMICAL_PME_TREATMENTS = {"direct-space": 0, "exact": 1}
+
+
+def alchemical_pme_treatment_code(name):
+    """BLUES_ALCH_PME_* of openmmtools' alchemical_pme_treatment name; ValueError for anything but the two supported values."""
+    if not isinstance(name, str) or name not in ALCHEMICAL_PME_TREATMENTS:
+        raise ValueError("alchemical_pme_treatment %r is not supported: the engine implements 'direct-space' and 'exact'" % (name,))
+    return ALCHEMICAL_PME_TREATMENTS[name]
+
+
 class BluesMinimizeDesc(C.Structure):
     """include/blues_engine.h: BluesMinimizeDesc (the constants of the device-resident FIRE minimiser)."""
     _fields_ = [
@@ -100,7 +116,8 @@ class BluesMinimizeResult(C.Structure):
 
 MINIMIZE_FIELDS = ("dt0", "dt_max", "f_inc", "f_dec", "alpha0", "f_alpha", "max_step", "n_min")
 # additive entry points (BLUES_ABI_VERSION unchanged): a library built before them loads, and the wrappers that need them say so
-OPTIONAL_SYMBOLS = ("blues_minimize_default", "blues_minimize", "blues_batch_minimize")
+MINIMIZE_SYMBOLS = ("blues_minimize_default", "blues_minimize", "blues_batch_minimize")
+OPTIONAL_SYMBOLS = MINIMIZE_SYMBOLS + ("blues_engine_create_ext", "blues_get_exact_pme_path")
 
 
 class BluesTuning(C.Structure):
@@ -201,10 +218,41 @@ class SystemData:
     custom_pair_mode: int = PAIR_STANDARD  # NB_NOCUTOFF only; PAIR_ETHYLENE: q/r^2 + lambda-scaled 12-6 between alchemical and non-alchemical atoms
     centroid_bonds: tuple = ()           # NB_NOCUTOFF only; entries (idx1, w1, idx2, w2, k): E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w)
     implicit_solvent: ImplicitSolventData = None   # NB_NOCUTOFF only; GB-OBC with the ACE surface term (blues_engine_create_gb)
+    alchemical_pme_treatment: str = "direct-space"   # NB_PME: "direct-space" or "exact" (openmmtools' alchemical_pme_treatment; blues_engine_create_ext)
+
+    def __post_init__(self):
+        alchemical_pme_treatment_code(self.alchemical_pme_treatment)
 
     @property
     def n_atoms(self):
         return int(len(self.mass))
+
+    def check_alchemical_pme_treatment(self, integrator=None):
+        """What blues_engine_create_ext refuses about the treatment (with `integrator`, an IntegratorData: about the pair), raised
+        before a library is loaded (ValueError)."""
+        if alchemical_pme_treatment_code(self.alchemical_pme_treatment) == 0:
+            return
+        if int(self.nonbonded_method) != NB_PME or not all(int(k) > 0 for k in tuple(self.pme_grid)):
+            raise ValueError("alchemical_pme_treatment 'exact' needs nonbonded_method = PME with a mesh: without reciprocal space "
+                             "(NoCutoff, direct-space-only PME) there is nothing for it to treat")
+        if not self.annihilate_electrostatics:
+            raise ValueError("alchemical_pme_treatment 'exact' needs annihilate_electrostatics = 1: the alchemical charges are scaled by "
+                             "lambda_electrostatics as a whole (exact PME can only annihilate)")
+        if integrator is not None and (integrator.measure_shadow_work or integrator.measure_heat):
+            raise ValueError("alchemical_pme_treatment 'exact' together with measure_shadow_work / measure_heat is not supported: the energy "
+                             "ledger's device-side energy sum does not know the exact treatment's partials")
+        if integrator is not None and int(integrator.switching_mode) != 0:
+            raise ValueError("alchemical_pme_treatment 'exact' with a switching_mode integrator is not supported: its force and energy "
+                             "bookkeeping does not know the exact treatment's terms")
+
+    def ext_desc(self):
+        """BluesSystemExt of this System, or None where blues_engine_create / blues_engine_create_gb say everything."""
+        code = alchemical_pme_treatment_code(self.alchemical_pme_treatment)
+        if code == 0:
+            return None
+        d = BluesSystemExt()
+        d.struct_size = C.sizeof(BluesSystemExt); d.alchemical_pme_treatment = code
+        return d
 
     def check_custom_forces(self):
         """What blues_engine_create refuses about the two custom forces, raised before a library is loaded (ValueError)."""
@@ -380,6 +428,7 @@ def declare_engine_prototypes(lib):
     protos = {
         "blues_engine_create": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.c_int, C.POINTER(H)], C.c_int),
         "blues_engine_create_gb": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_int, C.POINTER(H)], C.c_int),
+        "blues_engine_create_ext": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.POINTER(BluesSystemExt), C.c_int, C.POINTER(H)], C.c_int),
         "blues_engine_destroy": ([H], C.c_int),
         "blues_last_error": ([H], C.c_char_p),
         "blues_abi_version": ([], C.c_int),
@@ -404,6 +453,7 @@ def declare_engine_prototypes(lib):
         "blues_set_global": ([H, C.c_char_p, C.c_double], C.c_int),
         "blues_reset": ([H], C.c_int),
         "blues_get_stats": ([H, C.POINTER(C.c_int64)], C.c_int),
+        "blues_get_exact_pme_path": ([H, C.POINTER(C.c_int64)], C.c_int),
         "blues_time_nonbonded": ([H, C.c_int32, _dp], C.c_int),
         "blues_time_list_build": ([H, C.c_int32, _dp], C.c_int),
         "blues_audit_lists": ([H, C.POINTER(C.c_int64)], C.c_int),
@@ -450,12 +500,12 @@ def declare_engine_prototypes(lib):
 
 
 ENGINE_SYMBOLS = (
-    "blues_engine_create", "blues_engine_create_gb", "blues_engine_destroy", "blues_last_error", "blues_abi_version",
+    "blues_engine_create", "blues_engine_create_gb", "blues_engine_create_ext", "blues_engine_destroy", "blues_last_error", "blues_abi_version",
     "blues_tuning_default", "blues_set_tuning", "blues_get_tuning",
     "blues_set_positions", "blues_set_velocities", "blues_set_box", "blues_get_positions",
     "blues_get_velocities", "blues_get_forces", "blues_get_box", "blues_set_velocities_to_temperature",
     "blues_get_energy", "blues_get_energy_at", "blues_get_energy_terms", "blues_mesh_energy", "blues_step", "blues_run_switch", "blues_get_global",
-    "blues_set_global", "blues_reset", "blues_get_stats", "blues_time_nonbonded", "blues_time_list_build", "blues_audit_lists",
+    "blues_set_global", "blues_reset", "blues_get_stats", "blues_get_exact_pme_path", "blues_time_nonbonded", "blues_time_list_build", "blues_audit_lists",
     "blues_snapshot_capture", "blues_snapshot_release", "blues_snapshot_read", "blues_set_positions_from_snapshot",
     "blues_set_velocities_from_snapshot", "blues_snapshot_read_atoms", "blues_set_positions_from_snapshot_edited",
     "blues_batch_create", "blues_batch_destroy", "blues_batch_last_error", "blues_batch_size", "blues_batch_step", "blues_batch_set_active", "blues_batch_prefetch_energies",

@@ -129,7 +129,7 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
                       rigid_water=True, hydrogen_mass=None, remove_cm_motion=True, alchemical_atoms=(),
                       tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME",
                       implicit_solvent=None, solute_dielectric=1.0, solvent_dielectric=78.5, implicit_solvent_kappa=None,
-                      implicit_solvent_salt_conc=None):
+                      implicit_solvent_salt_conc=None, alchemical_pme_treatment="direct-space"):
     """Amber topology -> SystemData, following structure.createSystem's kwargs
     (reference examples/rotmove_cuda.yml:19-27: PME, 10 A cutoff, HBonds,
     rigidWater, removeCMMotion, hydrogenMass 3.024, ewaldErrorTolerance 0.005).
@@ -142,7 +142,11 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     no mesh and no dispersion correction; `box` may be None (the box is then stored as zeros and has no effect).
     implicit_solvent="OBC1" | "OBC2" (createSystem(implicitSolvent=app.OBC1 / app.OBC2, soluteDielectric, solventDielectric), reference
     blues/simulation.py:139-219): GB-OBC with the ACE surface term on a NoCutoff System, radii from %FLAG RADII and scale factors
-    from %FLAG SCREEN.  HCT, GBn, GBn2 and salt screening (kappa, a salt concentration) are not implemented and raise."""
+    from %FLAG SCREEN.  HCT, GBn, GBn2 and salt screening (kappa, a salt concentration) are not implemented and raise.
+    alchemical_pme_treatment="direct-space" | "exact" (SystemFactory.generateAlchSystem(..., alchemical_pme_treatment=...), reference
+    blues/simulation.py:236, 274-284): how full PME treats the alchemical charges; "exact" needs reciprocal space.  'coulomb' raises."""
+    from ._abi import alchemical_pme_treatment_code
+    alchemical_pme_treatment_code(alchemical_pme_treatment)
     if nonbonded_method not in ("PME", "NoCutoff"):
         raise ValueError("nonbonded_method must be 'PME' or 'NoCutoff', got %r" % (nonbonded_method,))
     no_cutoff = nonbonded_method == "NoCutoff"
@@ -325,7 +329,8 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
         nonbonded_method=method, cutoff=cutoff, ewald_alpha=alpha,
         remove_cm_motion=remove_cm_motion, positions=np.asarray(positions, dtype=np.float64),
         residue_of_atom=residue_of_atom, names=list(prm.get("ATOM_NAME", [])),
-        implicit_solvent=gb,
+        implicit_solvent=gb, alchemical_pme_treatment=alchemical_pme_treatment,
     )
     system.check_implicit_solvent()
+    system.check_alchemical_pme_treatment()
     return system

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -360,6 +361,12 @@ struct BluesEngine {
     DBuf<double> d_qn, d_qn_full, d_frec, d_pme_e; DBuf<int> d_pme_frozen; DBuf<unsigned long long> d_pme_acc;
     PmeBufs<float> pme_f; PmeBufs<double> pme_d;
     bool pme_static_valid = false;
+    // exact PME treatment of the alchemical charges (kernels_pme.h: k_pme_exact_b): the correction pairs, the per-slot force
+    // slab and the energy partials k_finalize reads through its fgb / gb_epart arguments, the box constants of E1 and E2
+    bool pme_exact = false; int pmex_n_pair = 0, pmex_n_row = 0; double pmex_c1 = 0.0, pmex_c2 = 0.0;
+    DBuf<unsigned long long> d_pmex_acc; DBuf<int> d_pmex_pi, d_pmex_pj, d_pmex_pk, d_pmex_ra, d_pmex_rs, d_pmex_ej, d_pmex_ek;
+    DBuf<double> d_pmex_pq, d_pmex_eq, d_fex, d_pmex_e; DBuf<int> d_pmex_path;   // (d_pmex_path: launches per mesh path, counted by the kernel)
+    DBuf<PmeExArgs<float>> d_pmex_rec_f; DBuf<PmeExArgs<double>> d_pmex_rec_d; long long pmex_rec_epoch = -1;   // a lone engine's own record (launch_pme_exact)
     double e_ewald_const = 0.0, e_disp = 0.0;   // self term + neutralising background; dispersion correction (functions of the box)
     // bonded
     DBuf<int> d_row_atom, d_row_start, d_ent_type, d_ent_term, d_ent_role;
@@ -419,6 +426,7 @@ struct BluesBatch {
     struct EvPair { hipEvent_t a = nullptr, b = nullptr; bool busy = false; };
     std::vector<const BluesEngine*> congr_lead; std::vector<uint64_t> congr_le, congr_me;   // congruence already established (batch_do_steps)
     bool defer_work = false; std::vector<DevAccum*> h_wacc; std::vector<double> h_wdelta; DBuf<DevAccum*> d_wacc; DBuf<double> d_wdelta;   // add_work of all members in one launch
+    DBuf<PmeExArgs<float>> d_pmex_f; DBuf<PmeExArgs<double>> d_pmex_d;   // members with the exact PME treatment: the records of k_pme_exact_b (batch_refresh_args)
     DBuf<GbArgs> d_gb;   // NoCutoff members with implicit solvent: the records of kernels_gb.h (batch_refresh_args)
     DBuf<NcArgs> d_nc;   // NoCutoff members: the records of the all-pairs kernel (batch_refresh_args)
     DBuf<FireState*> d_fire_ptrs; DBuf<FireState> d_fire_out;
@@ -1952,6 +1960,7 @@ static FinArgs make_fin_args(BluesEngine* h, const double le[3], int slot_mask =
     F.mass = h->d_mass.p; F.mom_part = h->d_mom_part.p;
     F.frec = h->pme ? h->d_frec.p : nullptr;
     if (h->gb_model) { F.fgb = h->d_fgb.p; F.gb_epart = h->d_gb_epart.p; F.gb_blocks = h->gb_blocks; }
+    if (h->pme_exact) { F.fgb = h->d_fex.p; F.gb_epart = h->d_pmex_e.p; F.gb_blocks = 1; }   // (exact PME treatment: the same E0 + le E1 + le^2 E2 channel, one block of partials)
     return F;
 }
 
@@ -2068,6 +2077,14 @@ template <typename T> static int pme_tables(BluesEngine* h) {
     for (double q : h->T->qn) { qsum += q; q2 += q * q; }
     const double V = h->box[0] * h->box[1] * h->box[2];
     h->e_ewald_const = -ONE_4PI_EPS0 * h->alpha / std::sqrt(M_PI) * q2 - M_PI * ONE_4PI_EPS0 * qsum * qsum / (2.0 * V * h->alpha * h->alpha);
+    if (h->pme_exact) {   // exact treatment: the alchemical charges' share of both constants, by class (q~ = le q)
+        double qa = 0.0, qa2 = 0.0;
+        for (int i : h->alch) { qa += h->T->charge[i]; qa2 += h->T->charge[i] * h->T->charge[i]; }
+        const double bg = -M_PI * ONE_4PI_EPS0 / (2.0 * V * h->alpha * h->alpha);
+        h->pmex_c1 = bg * 2.0 * qsum * qa;
+        h->pmex_c2 = -ONE_4PI_EPS0 * h->alpha / std::sqrt(M_PI) * qa2 + bg * qa * qa;
+        h->pmex_rec_epoch = -1;   // (a lone engine's record carries them)
+    }
     h->e_disp = 0.0;
     if (h->disp_corr) {   // [recalled: OpenMM NonbondedForceImpl::calcDispersionCorrection without switching function]; alchemical atoms enter with epsilon 0
         std::vector<double> cs, ce; std::vector<long long> cn;
@@ -2153,6 +2170,64 @@ template <typename T> static int launch_pme_t(BluesEngine* h, int want_energy) {
 static int launch_pme(BluesEngine* h, int want_energy) {
     if (!h->pme) return 0;
     return h->precision == 0 ? launch_pme_t<float>(h, want_energy) : launch_pme_t<double>(h, want_energy);
+}
+
+// exact PME treatment: the alchemical class of reciprocal space and the correction pairs, behind the environment's launch above (same
+// stream; it reads the static potential mesh and reuses the work meshes).  One kernel over member records: a lone engine launches it
+// over its own one record, so a batch member runs the lone chain's machine code.
+template <typename T> static PmeExArgs<T> make_pmex_args(BluesEngine* h) {
+    PmeExArgs<T> X; memset(&X, 0, sizeof X);
+    X.P = make_pme_args<T>(h, false); X.active = 1;
+    X.n_alch = (int)h->alch.size(); X.alch = h->d_alch_orig.p; X.q = h->d_qn_full.p; X.alch_local = h->d_alch_local.p; X.mobile_index = h->d_mobile_index.p;
+    X.acc2 = h->d_pmex_acc.p;
+    X.n_pair = h->pmex_n_pair; X.pair_i = h->d_pmex_pi.p; X.pair_j = h->d_pmex_pj.p; X.pair_qq = h->d_pmex_pq.p; X.pair_kind = h->d_pmex_pk.p;
+    X.n_row = h->pmex_n_row; X.row_atom = h->d_pmex_ra.p; X.row_start = h->d_pmex_rs.p; X.ent_j = h->d_pmex_ej.p; X.ent_qq = h->d_pmex_eq.p; X.ent_kind = h->d_pmex_ek.p;
+    X.alpha = h->alpha; X.rc2 = h->cutoff * h->cutoff; X.c1 = h->pmex_c1; X.c2 = h->pmex_c2;
+    X.fex = h->d_fex.p; X.epart = h->d_pmex_e.p; X.path = h->d_pmex_path.p;
+    return X;
+}
+template <typename T> static DBuf<PmeExArgs<T>>& pmex_rec(BluesEngine* h) { if constexpr (sizeof(T) == 4) return h->d_pmex_rec_f; else return h->d_pmex_rec_d; }
+template <typename T> static DBuf<PmeExArgs<T>>& pmex_recs(BluesBatch* B) { if constexpr (sizeof(T) == 4) return B->d_pmex_f; else return B->d_pmex_d; }
+template <typename T> static int launch_pme_exact_t(BluesEngine* h, const double le[3]) {
+    if (batch_dry(h)) return 0;
+    PmeExDyn d; for (int s = 0; s < 3; s++) d.le[s] = le[s];
+    // the same choice as launch_pme_t: mixed precision with a mesh whose half spectrum fits LDS takes the pruned in-LDS pipeline
+    // (k_pme_exact_fast_b, which falls back per member where the atoms or their blocks do not fit)
+    bool fast = false; size_t lds = 0;
+    if constexpr (sizeof(T) == 4) {
+        fast = (size_t)h->pme_K[0] * h->pme_K[1] * (h->pme_K[2] / 2 + 1) <= PME_LDS_Y && !h->tune.pme_general;
+        lds = PME_FAST_LDS(h->pme_K[0], h->pme_K[1], h->pme_K[2]);
+        static thread_local size_t lds_set = 0;
+        if (fast && lds > lds_set) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pme_exact_fast_b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) E_FAIL(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+            lds_set = lds;
+        }
+    }
+    if (batch_lead(h)) {
+        if constexpr (sizeof(T) == 4) {
+            if (fast) hipLaunchKernelGGL(k_pme_exact_fast_b, dim3(h->batch->R()), dim3(PME_THREADS), lds, h->cur, pmex_recs<T>(h->batch).p, d);
+            else hipLaunchKernelGGL(k_pme_exact_b<T>, dim3(h->batch->R()), dim3(PME_THREADS), 0, h->cur, pmex_recs<T>(h->batch).p, d);
+        } else hipLaunchKernelGGL(k_pme_exact_b<T>, dim3(h->batch->R()), dim3(PME_THREADS), 0, h->cur, pmex_recs<T>(h->batch).p, d);
+    } else {
+        if (h->pmex_rec_epoch != (long long)h->args_epoch) {
+            std::vector<PmeExArgs<T>> rec(1, make_pmex_args<T>(h));
+            HIP_OK(h, hipStreamSynchronize(h->cur));   // (the record may be in use by a launch still in flight)
+            try { pmex_rec<T>(h).upload(rec); } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+            h->pmex_rec_epoch = (long long)h->args_epoch;
+        }
+        if constexpr (sizeof(T) == 4) {
+            if (fast) hipLaunchKernelGGL(k_pme_exact_fast_b, dim3(1), dim3(PME_THREADS), lds, h->cur, pmex_rec<T>(h).p, d);
+            else hipLaunchKernelGGL(k_pme_exact_b<T>, dim3(1), dim3(PME_THREADS), 0, h->cur, pmex_rec<T>(h).p, d);
+        } else hipLaunchKernelGGL(k_pme_exact_b<T>, dim3(1), dim3(PME_THREADS), 0, h->cur, pmex_rec<T>(h).p, d);
+    }
+    h->st_launches++;
+    HIP_OK(h, hipGetLastError());
+    return 0;
+}
+static int launch_pme_exact(BluesEngine* h, const double le[3]) {
+    if (!h->pme_exact) return 0;
+    return h->precision == 0 ? launch_pme_exact_t<float>(h, le) : launch_pme_exact_t<double>(h, le);
 }
 
 static int resolve_xfer(BluesEngine* h) {
@@ -2379,6 +2454,7 @@ static int force_pass(BluesEngine* h, int base_L) {
         if (!fused && launch_bonded(h, true)) return 1;
     }
     if (h->gb_model && launch_gb_p<false>(h, le)) return 1;   // (implicit solvent: a NoCutoff engine takes the serial schedule above)
+    if (launch_pme_exact(h, le)) return 1;   // (exact PME treatment: behind the environment's mesh launch on the main stream, before the sums)
     if (launch_finalize_deferred(h, le, fmask)) return 1;
     h->pass_valid = true; h->pass_L = base_L; h->st_passes++; h->vel_clean = true; h->acc_cache_valid = false;
     HIP_OK(h, hipGetLastError());
@@ -2504,6 +2580,7 @@ static int energy_launch(BluesEngine* h) {
     if (rc) return 1;
     if (h->gb_model && launch_gb_p<true>(h, le)) return 1;
     if (launch_pme(h, 1)) return 1;
+    if (launch_pme_exact(h, le)) return 1;
     const EnergyShape g = energy_shape(h);
     if (g.nbb > 0) {
         pick_tag<std::true_type, std::false_type>(h->n_cent > 0, [&](auto cent) {   // (with / without centroid bonds)
@@ -2541,6 +2618,10 @@ static void energy_sum(BluesEngine* h, const double* enb, const double* eb, int 
         const double le = h->cur_le;
         T[8] = c[0] + le * (c[1] + le * c[2]); T[9] = c[3] + le * c[4];
         if (one) { one[2] = c[0] + (c[1] + c[2]); one[3] = c[3] + c[4]; }
+    } else if (h->pme_exact && egb) {   // exact PME treatment (kernels_pme.h): [1] E1, [2] E2 + C_aa, [5] C_aa, the direct-space alchemical x alchemical sum that takes le^2
+        const double le = h->cur_le, e2 = egb[2] - egb[5];
+        if (one) { one[2] = T[8] + (egb[1] + e2); one[3] = T[9]; }   // (at le = 1 the C_aa correction of term [6] vanishes)
+        T[8] += le * (egb[1] + le * e2); T[6] += (le * le - le) * egb[5];
     } else if (one) { one[2] = T[8]; one[3] = T[9]; }
 }
 
@@ -2571,6 +2652,7 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
     std::vector<double> enb, eb, ep, egb; std::vector<int> jc;
     try {
         if (h->gb_model) h->d_gb_epart.download(egb);
+        if (h->pme_exact) h->d_pmex_e.download(egb);
         h->d_epart_nb.download(enb);
         if (!h->e_frozen_valid) {
             h->e_frozen[0] = h->e_frozen[1] = 0.0;
@@ -2583,7 +2665,7 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
     double e_mesh = 0.0;
     if (h->pme) HIP_OK(h, hipMemcpy(&e_mesh, h->d_pme_e.p, sizeof e_mesh, hipMemcpyDeviceToHost));
     double one[4], E, E_one;
-    energy_sum(h, enb.data(), eb.data(), h->alch.empty() ? 0 : jc[h->n_lists], ep.data(), e_mesh, T, one, h->gb_model ? egb.data() : nullptr);
+    energy_sum(h, enb.data(), eb.data(), h->alch.empty() ? 0 : jc[h->n_lists], ep.data(), e_mesh, T, one, (h->gb_model || h->pme_exact) ? egb.data() : nullptr);
     energy_totals(h, T, one, &E, &E_one);
     h->ecache.put(1.0, 1.0, E_one); h->ecache.put(h->cur_ls, h->cur_le, E);   // (the current parameters last: they win when both are (1, 1))
     return 0;
@@ -2933,6 +3015,7 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
     if (nocut(a) != nocut(b)) { *why = "nonbonded method (a NoCutoff engine and a periodic one cannot share a batch)"; return false; }
     if (a->led_flags != b->led_flags) { *why = "measure_shadow_work / measure_heat (measuring and non-measuring members cannot share a batch)"; return false; }
     if (a->pair_mode != b->pair_mode || a->n_cent != b->n_cent) { *why = "custom forces (members with and without the custom pair form or centroid bonds cannot share a batch)"; return false; }
+    if (a->pme_exact != b->pme_exact) { *why = "alchemical_pme_treatment (members with the exact and the direct-space treatment cannot share a batch)"; return false; }
     if ((a->gb_model != 0) != (b->gb_model != 0)) { *why = "implicit solvent (members with and without it cannot share a batch)"; return false; }
     if (a->gb_model != b->gb_model || a->gb_eps_in != b->gb_eps_in || a->gb_eps_out != b->gb_eps_out || a->gb_sa_energy != b->gb_sa_energy || a->gb_radius != b->gb_radius || a->gb_scale != b->gb_scale) { *why = "implicit solvent (model, dielectrics, surface term, radii or scales differ)"; return false; }
 #define BC(f) if (a->f != b->f) { *why = #f; return false; }
@@ -2980,6 +3063,8 @@ static int batch_refresh_args(BluesBatch* B) {
     const bool with_gb = B->eng[0]->gb_model != 0;
     std::vector<GbArgs> gb(with_gb ? B->R() : 0);
     const bool single = B->eng[0]->precision == 0;
+    const bool with_pmex = B->eng[0]->pme_exact;
+    std::vector<PmeExArgs<float>> xf(with_pmex && single ? B->R() : 0); std::vector<PmeExArgs<double>> xd(with_pmex && !single ? B->R() : 0);
     if (single) nf.resize(B->R()); else nd.resize(B->R());
     for (int r = 0; r < B->R(); r++) {
         BluesEngine* h = B->eng[r];
@@ -2989,6 +3074,10 @@ static int batch_refresh_args(BluesBatch* B) {
         if (single) nf[r].active = B->rec_active[r]; else nd[r].active = B->rec_active[r];
         if (no_cutoff) { nc[r] = make_nc_args(h); nc[r].active = B->rec_active[r] && h->sorted_ok; }
         if (with_gb) { gb[r] = make_gb_args(h); gb[r].active = B->rec_active[r] && h->sorted_ok; }
+        if (with_pmex) {
+            if (single) { xf[r] = make_pmex_args<float>(h); xf[r].active = B->rec_active[r] && h->sorted_ok && h->pme_exact; }
+            else { xd[r] = make_pmex_args<double>(h); xd[r].active = B->rec_active[r] && h->sorted_ok && h->pme_exact; }
+        }
         if (!h->sorted_ok) { core[r].active = 0; if (single) nf[r].active = 0; else nd[r].active = 0; continue; }  // buffers not laid out (its sort failed): never touched
         core[r].al = make_alch_args(h, one, one, 7); core[r].bo = make_bonded_args(h); core[r].fin = make_fin_args(h, one); core[r].in = make_int_args(h);
         core[r].in.work_trace = h->d_trace.p;  // the launch decides whether it is written (IntDyn.tracing)
@@ -2999,7 +3088,7 @@ static int batch_refresh_args(BluesBatch* B) {
     }
     // the records may be in use by launches still in flight
     if (hipStreamSynchronize(B->stream) != hipSuccess) { B->err = "stream synchronisation failed"; return 1; }
-    try { B->d_core.upload(core); if (single) B->d_nb_f.upload(nf); else B->d_nb_d.upload(nd); if (no_cutoff) B->d_nc.upload(nc); if (with_gb) B->d_gb.upload(gb); } catch (std::string& e) { B->err = e; return 1; }
+    try { B->d_core.upload(core); if (single) B->d_nb_f.upload(nf); else B->d_nb_d.upload(nd); if (no_cutoff) B->d_nc.upload(nc); if (with_gb) B->d_gb.upload(gb); if (with_pmex) { if (single) B->d_pmex_f.upload(xf); else B->d_pmex_d.upload(xd); } } catch (std::string& e) { B->err = e; return 1; }
     return 0;
 }
 
@@ -3088,7 +3177,7 @@ static bool prefetch_potential(BluesBatch* B, BluesEngine* lead, std::vector<cha
     if (batch_section_begin(B, lead)) return false;
     bool ok = batch_each(B, true, [&](int r) { return live[r] != 0; }, [&](int r) { return energy_launch(B->eng[r]); }) < 0;
     const EnergyShape g = energy_shape(lead);
-    const int n_nb = 2 * g.nw, n_b = g.nbb * T_NTYPES, n_al = lead->alch.empty() ? 0 : (lead->k2_nblocks_env + 1) * K2_NP, n_gb = lead->gb_model ? lead->gb_blocks * GB_NE : 0, stride = n_nb + n_b + n_al + 2 + n_gb;
+    const int n_nb = 2 * g.nw, n_b = g.nbb * T_NTYPES, n_al = lead->alch.empty() ? 0 : (lead->k2_nblocks_env + 1) * K2_NP, n_gb = lead->gb_model ? lead->gb_blocks * GB_NE : (lead->pme_exact ? PMEX_NE : 0), stride = n_nb + n_b + n_al + 2 + n_gb;
     std::vector<double> slab; std::vector<int> hints;
     try {
         if (ok) {
@@ -3367,7 +3456,61 @@ int blues_get_tuning(BluesTuning* t) { *t = g_tuning; return 0; }
 
 const char* blues_last_error(const BluesEngine* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb) {
+// exact PME treatment: the correction pairs of k_pme_exact_b.  Kind 0 / 1: an excluded pair (exceptions included) that holds one / two
+// alchemical atoms -- its erf correction belongs to class a_i + a_j; kind 2: a non-excluded alchemical x alchemical pair, whose direct-space
+// Coulomb term the alchemical kernel scales with le and the exact treatment with le^2.  Unique pairs for the energies; for the forces
+// one row per mobile atom, its entries in this order.
+static int build_pmex_pairs(BluesEngine* h, const BluesSystemDesc* s) {
+    const std::vector<int>& al = h->T->alch_local; const std::vector<double>& q = h->T->charge;
+    std::vector<int> pi, pj, pk; std::vector<double> pq;
+    std::set<std::pair<int, int>> excl;
+    for (int e = 0; e < s->n_exclusions; e++) {
+        const int i = s->exclusions[2 * e], j = s->exclusions[2 * e + 1];
+        if (i == j || !excl.insert({std::min(i, j), std::max(i, j)}).second) continue;
+        const int cls = (al[i] >= 0) + (al[j] >= 0);
+        if (cls == 0 || q[i] * q[j] == 0.0) continue;
+        pi.push_back(i); pj.push_back(j); pq.push_back(q[i] * q[j]); pk.push_back(cls - 1);
+    }
+    for (size_t a = 0; a < h->alch.size(); a++) for (size_t b = a + 1; b < h->alch.size(); b++) {
+        const int i = h->alch[a], j = h->alch[b];
+        if (excl.count({std::min(i, j), std::max(i, j)}) || q[i] * q[j] == 0.0) continue;
+        pi.push_back(i); pj.push_back(j); pq.push_back(q[i] * q[j]); pk.push_back(2);
+    }
+    std::vector<std::vector<int>> of(h->n);
+    for (size_t p = 0; p < pi.size(); p++) { if (h->T->mass[pi[p]] != 0.0) of[pi[p]].push_back((int)p); if (h->T->mass[pj[p]] != 0.0) of[pj[p]].push_back((int)p); }
+    std::vector<int> ra, rs(1, 0), ej, ek; std::vector<double> eq;
+    for (int i = 0; i < h->n; i++) {
+        if (of[i].empty()) continue;
+        ra.push_back(i);
+        for (int p : of[i]) { ej.push_back(pi[p] == i ? pj[p] : pi[p]); eq.push_back(pq[p]); ek.push_back(pk[p]); }
+        rs.push_back((int)ej.size());
+    }
+    h->pmex_n_pair = (int)pi.size(); h->pmex_n_row = (int)ra.size();
+    if (pi.empty()) { pi.push_back(0); pj.push_back(0); pk.push_back(0); pq.push_back(0.0); }   // (no empty device buffers: the counts say what is read)
+    if (ra.empty()) ra.push_back(0);
+    if (ej.empty()) { ej.push_back(0); ek.push_back(0); eq.push_back(0.0); }
+    try {
+        h->d_pmex_pi.upload(pi); h->d_pmex_pj.upload(pj); h->d_pmex_pk.upload(pk); h->d_pmex_pq.upload(pq);
+        h->d_pmex_ra.upload(ra); h->d_pmex_rs.upload(rs); h->d_pmex_ej.upload(ej); h->d_pmex_ek.upload(ek); h->d_pmex_eq.upload(eq);
+        h->d_pmex_acc.alloc((size_t)h->pme_K[0] * h->pme_K[1] * h->pme_K[2]); h->d_fex.alloc((size_t)9 * h->n); h->d_pmex_e.alloc(PMEX_NE); h->d_pmex_path.upload(std::vector<int>(2, 0));
+        HIP_OK(h, hipMemset(h->d_fex.p, 0, sizeof(double) * 9 * h->n));
+    } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+    return 0;
+}
+
+static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, const BluesSystemExt* ext) {
+    if (ext) {   // alchemical_pme_treatment: what the exact treatment refuses, each with its reason
+        if (ext->struct_size != (int32_t)sizeof(BluesSystemExt)) E_FAIL(h, "BluesSystemExt: struct_size %d does not match this library's %d", ext->struct_size, (int)sizeof(BluesSystemExt));
+        const int tr = ext->alchemical_pme_treatment;
+        if (tr != BLUES_ALCH_PME_DIRECT_SPACE && tr != BLUES_ALCH_PME_EXACT) E_FAIL(h, "alchemical_pme_treatment %d: the engine knows 0 ('direct-space') and 1 ('exact')", tr);
+        if (tr == BLUES_ALCH_PME_EXACT) {
+            if (s->nonbonded_method != BLUES_NB_PME || s->pme_grid[0] <= 0 || s->pme_grid[1] <= 0 || s->pme_grid[2] <= 0) E_FAIL(h, "alchemical_pme_treatment 'exact' needs nonbonded_method = PME with a mesh: without reciprocal space there is nothing for it to treat");
+            if (!s->annihilate_electrostatics) E_FAIL(h, "alchemical_pme_treatment 'exact' needs annihilate_electrostatics = 1: the alchemical charges are scaled by lambda_electrostatics as a whole (exact PME can only annihilate)");
+            if (it->measure_shadow_work || it->measure_heat) E_FAIL(h, "alchemical_pme_treatment 'exact' together with measure_shadow_work / measure_heat is not supported: the energy ledger's device-side energy sum does not know the exact treatment's partials");
+            if (it->switching_mode != BLUES_SWITCH_NONE) E_FAIL(h, "alchemical_pme_treatment 'exact' with a switching_mode integrator is not supported: its force and energy bookkeeping does not know the exact treatment's terms");
+            h->pme_exact = s->n_alchemical > 0;   // (no alchemical atom: both treatments are the plain System)
+        }
+    }
     if (gb && gb->model != BLUES_GB_NONE) {   // implicit solvent (kernels_gb.h): what such an engine refuses, each with its reason
         if (gb->model != BLUES_GB_OBC1 && gb->model != BLUES_GB_OBC2) E_FAIL(h, "implicit solvent: model %d; the engine knows 1 (OBC1) and 2 (OBC2)", gb->model);
         if (s->nonbonded_method != BLUES_NB_NOCUTOFF) E_FAIL(h, "implicit solvent needs nonbonded_method = NoCutoff: GB has no periodic or cutoff form here");
@@ -3506,6 +3649,7 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
     }
     h->cur = h->stream;
     if (h->tune.fast_step >= 0) h->fast_step = h->tune.fast_step != 0;
+    if (h->pme_exact) h->fast_step = false;   // exact PME treatment: the per-slot mesh force joins the sums in k_finalize (its fgb channel), which the fused step kernels do not have
     if (h->led_flags) h->fast_step = false;   // a measuring engine steps through the general interpreter and k_finalize: the fused step kernels stay as they are
     try {
         for (int k = 0; k < 3; k++) { h->d_x[k].alloc(n); h->d_v[k].alloc(n); h->d_xbuild[k].alloc(n); h->d_x_sort[k].alloc(n); }
@@ -3531,6 +3675,7 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
     if (build_clusters(h, s)) return 1;
     // (the fragments of kernels_frag.h are cut when a layout first asks for them: sort_and_tile)
     try { if (build_bonded(h, s)) return 1; } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
+    if (h->pme_exact && build_pmex_pairs(h, s)) return 1;
     if (no_cutoff && nocut_layout(h)) return 1;
     return 0;
 }
@@ -3571,7 +3716,8 @@ int blues_debug_check_guards(int64_t* out8) {
 int blues_debug_setup_seconds(double* out8) { if (!out8) return 2; for (int k = 0; k < 8; k++) out8[k] = g_setup_sec[k]; return 0; }
 
 int blues_engine_create(const BluesSystemDesc* s, const BluesIntegratorDesc* it, int device, BluesEngine** out) { return blues_engine_create_gb(s, it, nullptr, device, out); }
-int blues_engine_create_gb(const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, int device, BluesEngine** out) {
+int blues_engine_create_gb(const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, int device, BluesEngine** out) { return blues_engine_create_ext(s, it, gb, nullptr, device, out); }
+int blues_engine_create_ext(const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, const BluesSystemExt* ext, int device, BluesEngine** out) {
     SetupTimer tm_create(0);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available: the blues_amd engine has no CPU fallback"; return 2; }
@@ -3579,7 +3725,7 @@ int blues_engine_create_gb(const BluesSystemDesc* s, const BluesIntegratorDesc* 
     BluesEngine* h = new BluesEngine();
     h->device = device;
     int rc;
-    try { rc = create_impl(h, s, it, gb); } catch (std::string& e) { h->err = e; rc = 1; }
+    try { rc = create_impl(h, s, it, gb, ext); } catch (std::string& e) { h->err = e; rc = 1; }
     if (rc) { g_create_error = h->err; delete h; return rc; }
     *out = h;
     return 0;
@@ -3962,6 +4108,7 @@ static int current_force_pass(BluesEngine* h) {
     if (rc) return 1;
     if (launch_pme(h, 0)) return 1;
     if (h->gb_model && launch_gb_p<false>(h, le)) return 1;
+    if (launch_pme_exact(h, le)) return 1;
     return launch_bonded_and_finalize(h, le, false);
 }
 
@@ -4304,6 +4451,17 @@ int blues_get_stats(BluesEngine* h, int64_t stats[BLUES_N_STATS]) {
     return 0;
 }
 
+int blues_get_exact_pme_path(BluesEngine* h, int64_t out[2]) {
+    out[0] = out[1] = 0;
+    if (!h->pme_exact || !h->d_pmex_path.p) return 0;
+    int c[2];
+    hipSetDevice(h->device);
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    HIP_OK(h, hipMemcpy(c, h->d_pmex_path.p, sizeof c, hipMemcpyDeviceToHost));
+    out[0] = c[0]; out[1] = c[1];
+    return 0;
+}
+
 int blues_time_nonbonded(BluesEngine* h, int32_t reps, double* usec) {
     HIP_OK(h, hipSetDevice(h->device));
     if (flush_program(h)) return 1;
@@ -4388,6 +4546,7 @@ int blues_time_list_build(BluesEngine* h, int32_t reps, double* usec) {
 // every atom's own charge (what the non-alchemical System of the MD / alch contexts carries): include/blues_engine.h, blues_mesh_energy
 int blues_mesh_energy(BluesEngine* h, int32_t with_alchemical_charges, double* out) {
     if (!out) E_FAIL(h, "mesh energy: no output");
+    if (h->pme_exact) E_FAIL(h, "mesh energy: an engine with alchemical_pme_treatment 'exact' has no mesh differential (its System at lambda = (1, 1) differs from the plain one by box constants only)");
     HIP_OK(h, hipSetDevice(h->device));
     *out = 0.0;
     if (!h->pme) return 0;
@@ -4402,6 +4561,7 @@ int blues_mesh_energy(BluesEngine* h, int32_t with_alchemical_charges, double* o
 
 int blues_batch_mesh_energy(BluesBatch* B, int32_t with_alchemical_charges, const int32_t* mask, double* out) {
     if (!B || B->eng.empty() || !out) { if (B) B->err = "mesh energy: no batch / no output"; return 2; }
+    for (BluesEngine* m : B->eng) if (m->pme_exact) { B->err = "mesh energy: a member with alchemical_pme_treatment 'exact' has no mesh differential"; return 1; }
     const int R = B->R();
     if (hipSetDevice(B->eng[0]->device) != hipSuccess) { B->err = "hipSetDevice failed"; return 1; }
     for (int r = 0; r < R; r++) out[r] = 0.0;

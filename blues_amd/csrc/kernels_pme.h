@@ -473,3 +473,441 @@ __global__ void __launch_bounds__(PME_THREADS) k_pme_fast(PmeArgs<float> P) { pm
 
 template <typename T, bool STATIC>
 __global__ void __launch_bounds__(PME_THREADS) k_pme(PmeArgs<T> P) { pme_body<T, STATIC, 5>(P); }
+
+// ---- exact PME treatment of the alchemical charges: q~_i = lambda_electrostatics^a_i q_i in reciprocal space, the self
+// term, the neutralising background and the erf corrections of excluded pairs, so each of them is E0 + le E1 + le^2 E2 at fixed positions.
+// The launches above keep what they do for the environment class (alchemical atoms carry qn = 0 there: frec, the env-env mesh energy, the
+// static meshes of the frozen environment).  This kernel adds the second class.  The mobile environment charges are spread into the REAL
+// part of the charge mesh and the alchemical charges (mobile or frozen) into the IMAGINARY part: the reciprocal-space kernel is real in
+// real space (eterm(m) = eterm(-m)), the transforms are linear, so after the back transform the real part is the potential of the
+// mobile environment and the imaginary part the potential of the alchemical atoms -- two classes for the transforms of one.
+//   E1 = sum_a q_a phi_env(a) (+ background cross term + erf corrections of alchemical-environment exclusions)
+//   E2 = 1/2 sum_a q_a phi_alch(a) (+ alchemical self term and background + erf corrections of alchemical-alchemical exclusions)
+//   force per lambda slot: q_j le grad phi_alch on a mobile environment atom (q_j grad phi_env is frec), le q_a (grad phi_env + le grad phi_alch)
+//   on an alchemical atom.
+// The non-excluded alchemical x alchemical direct-space pairs, which the alchemical kernel scales with le, take le^2 here through a
+// pair correction C_aa (le^2 - le) (kind 2 below).  Sums run in fixed orders (64-bit fixed-point spread, lanes by wave_sum, waves in
+// wave order, an atom's pair entries in list order): a batch member equals the lone chain bit for bit.  One machine code serves both
+// (record form, blockIdx.x = member), as for kernels_gb.h.
+#define PMEX_NE 6   // energy partials, laid out like a GB block's for k_finalize: [1] E1, [2] E2 (+ C_aa), [4] -C_aa, [5] C_aa (read by the host only)
+template <typename T> struct PmeExArgs {
+    PmeArgs<T> P;                  // the engine's per-step arguments: meshes, tables, box, positions, sel = mobile atoms, qn
+    int active;                    // (batched form) 0: the member sits this launch out
+    int n_alch; const int* alch;   // alchemical atoms, caller indices
+    const double* q;               // [n] every atom's own charge
+    const int* alch_local;         // [n] >= 0: alchemical
+    const int* mobile_index;       // [n] >= 0: mobile
+    unsigned long long* acc2;      // [ng] fixed-point mesh of the alchemical class
+    int n_pair; const int* pair_i; const int* pair_j; const double* pair_qq; const int* pair_kind;   // unique pairs (energies)
+    int n_row; const int* row_atom; const int* row_start; const int* ent_j; const double* ent_qq; const int* ent_kind;   // per mobile atom (forces)
+    double alpha, rc2;
+    double c1, c2;                 // box constants: background cross term; alchemical self term + background
+    double* fex;                   // [9][n] force per slot (k_finalize's fgb)
+    double* epart;                 // [PMEX_NE]
+    int* path;                     // [2] launches served by the pruned in-LDS pipeline / by the general one
+};
+struct PmeExDyn { double le[3]; };
+
+// potential and gradient sums of the two classes at atom i: out[0..2] = sum of (dw w w, w dw w, w w dw) phi, out[3] = sum w w w phi
+template <typename T>
+__device__ __forceinline__ void pmex_gather(const PmeArgs<T>& P, int i, bool want_env, double env[4], double alc[4]) {
+    constexpr int ORDER = 5;
+    const int K0 = P.K[0], K1 = P.K[1], K2 = P.K[2];
+    int t0, t1, t2; T d0, d1, d2;
+    pme_locate(P, i, 0, t0, d0); pme_locate(P, i, 1, t1, d1); pme_locate(P, i, 2, t2, d2);
+    T w0[ORDER], w1[ORDER], w2[ORDER], e0[ORDER], e1[ORDER], e2[ORDER];
+    pme_splines_c<T, ORDER>(d0, w0, e0); pme_splines_c<T, ORDER>(d1, w1, e1); pme_splines_c<T, ORDER>(d2, w2, e2);
+    for (int k = 0; k < 4; k++) { env[k] = 0.0; alc[k] = 0.0; }
+#pragma unroll
+    for (int a = 0; a < ORDER; a++) {
+        int ix = t0 + a; if (ix >= K0) ix -= K0;
+#pragma unroll
+        for (int b = 0; b < ORDER; b++) {
+            int iy = t1 + b; if (iy >= K1) iy -= K1;
+            T sxe = (T)0, sze = (T)0, sxa = (T)0, sza = (T)0;
+#pragma unroll
+            for (int c = 0; c < ORDER; c++) {
+                int iz = t2 + c; if (iz >= K2) iz -= K2;
+                const size_t g = ((size_t)ix * K1 + iy) * K2 + iz;
+                const T pa = P.a_im[g];
+                sxa = fma(w2[c], pa, sxa); sza = fma(e2[c], pa, sza);
+                if (want_env) {
+                    const T pe = P.a_re[g] + (P.have_static ? P.phi_f[g] : (T)0);
+                    sxe = fma(w2[c], pe, sxe); sze = fma(e2[c], pe, sze);
+                }
+            }
+            alc[0] += (double)(e0[a] * w1[b] * sxa); alc[1] += (double)(w0[a] * e1[b] * sxa); alc[2] += (double)(w0[a] * w1[b] * sza); alc[3] += (double)(w0[a] * w1[b] * sxa);
+            env[0] += (double)(e0[a] * w1[b] * sxe); env[1] += (double)(w0[a] * e1[b] * sxe); env[2] += (double)(w0[a] * w1[b] * sze); env[3] += (double)(w0[a] * w1[b] * sxe);
+        }
+    }
+}
+
+// one correction pair: kind 0 / 1 = erf correction of an excluded pair of class 1 / 2, kind 2 = direct-space alchemical x alchemical pair
+// (class 2 minus the class 1 the alchemical kernel gives it).  d = x_i - x_j; returns the energy, *fs = force scale (force on i = fs d)
+template <typename T>
+__device__ __forceinline__ double pmex_pair(const PmeExArgs<T>& X, int i, int j, double qq, int kind, double d[3], double* fs) {
+    const PmeArgs<T>& P = X.P;
+    for (int k = 0; k < 3; k++) d[k] = min_image_d(P.x[k][i] - P.x[k][j], P.box.L[k], P.box.invL[k]);
+    const double r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    if (kind == 2) {
+        if (!(r2 < X.rc2)) { *fs = 0.0; return 0.0; }
+        return coulomb_d(r2, qq, X.alpha, true, fs);
+    }
+    const double pre = ONE_4PI_EPS0 * qq, al = X.alpha, r = sqrt(r2), er = erf(al * r);
+    const double dEdr = -pre * (TWO_OVER_SQRT_PI * al * exp(-al * al * r2) / r - er / r2);
+    *fs = -dEdr / r;
+    return -pre * er / r;
+}
+
+
+// ---- the alchemical class on the pruned in-LDS pipeline (mixed precision; the layout, the passes and the fixed-point spread of k_pme_fast).
+// Two runs of the pipeline in one workgroup, each with its own small block in and its own block out:
+//   1. the mobile environment charges, spread over the block U of all charged mobile and alchemical atoms, transformed back onto the block A
+//      of the alchemical atoms only: phi_env there (plus the frozen environment's static potential mesh, read at the <= 64 atoms' stencils);
+//   2. the alchemical charges, spread over A, transformed back onto U: phi_alch at every mobile atom and at the alchemical atoms.
+// (k_pme_fast, whose body the direct-space treatment runs, keeps its mobile potential in LDS and is left as it is; run 1 repeats its
+// spread and forward passes in LDS and prunes the backward passes to A.)  Entries of the atom cache: the mobile atoms (P.sel), then the
+// alchemical atoms (mobile or frozen).  Per-atom sums over a stencil are taken by 32 lanes in a fixed shuffle order, the energies over
+// the alchemical atoms by wave 0: a batch member equals the lone chain bit for bit.  Returns false (block-uniform, nothing written) when the
+// blocks or the atoms do not fit the buffers: the caller then takes the general path.
+#define PMEX_LDS_ATOMS (PME_LDS_ATOMS - 128)   // cache entries; the last 128 slots (4 KiB) hold the alchemical atoms' gathered sums
+#define PMEX_MAX_ALCH 64
+
+// one run: the block Ri of the charge mesh (32-bit fixed point at Y) -> the potential on the block Ro (real part of X[Lox][Loy][Loz])
+__device__ __forceinline__ void pmex_fast_pipeline(const PmeArgs<float>& P, const PmeRegion& Ri, const PmeRegion& Ro) {
+    const int X = 0, Y = PME_LDS_X, tw0 = PME_LDS_X + PME_LDS_Y, tw1 = tw0 + P.K[0], tw2 = tw1 + P.K[1];
+    const int tid = threadIdx.x, K0 = P.K[0], K1 = P.K[1], K2 = P.K[2], Hz = K2 / 2 + 1;
+    const int Lix = Ri.L[0], Liy = Ri.L[1], Liz = Ri.L[2], Lox = Ro.L[0], Loy = Ro.L[1], Loz = Ro.L[2];
+    const int* acc = reinterpret_cast<const int*>(pme_lds + Y);
+    for (int g = tid; g < Lix * Liy * Liz; g += PME_THREADS) pme_lds[X + g] = make_float2((float)acc[g] * (1.0f / PME_FIX32), 0.0f);
+    __syncthreads();
+    pme_pass<-1>(X, Y, Lix * Liy, Liy, Liy * Liz, Liz, 1, Liz, Ri.s[2], Liy * Hz, Hz, 1, Hz, 0, K2, tw2); __syncthreads();
+    pme_pass<-1>(Y, X, Lix * Hz, Hz, Liy * Hz, 1, Hz, Liy, Ri.s[1], K1 * Hz, 1, Hz, K1, 0, K1, tw1); __syncthreads();
+    pme_pass<-1>(X, Y, K1 * Hz, Hz, Hz, 1, K1 * Hz, Lix, Ri.s[0], Hz, 1, K1 * Hz, K0, 0, K0, tw0); __syncthreads();
+    for (int g = tid; g < K0 * K1 * Hz; g += PME_THREADS) {   // eterm and the weight of the half spectrum's missing conjugates
+        const int kz = g % Hz, xy = g / Hz;
+        const float et = P.eterm[(size_t)xy * K2 + kz] * ((kz == 0 || 2 * kz == K2) ? 1.0f : 2.0f);
+        pme_lds[Y + g].x *= et; pme_lds[Y + g].y *= et;
+    }
+    __syncthreads();
+    pme_pass<1>(Y, X, K1 * Hz, Hz, Hz, 1, K1 * Hz, K0, 0, Hz, 1, K1 * Hz, Lox, Ro.s[0], K0, tw0); __syncthreads();
+    pme_pass<1>(X, Y, Lox * Hz, Hz, K1 * Hz, 1, Hz, K1, 0, Loy * Hz, 1, Hz, Loy, Ro.s[1], K1, tw1); __syncthreads();
+    pme_pass<1>(Y, X, Lox * Loy, Loy, Loy * Hz, Hz, 1, Hz, 0, Loy * Loz, Loz, 1, Loz, Ro.s[2], K2, tw2); __syncthreads();
+}
+
+__device__ __forceinline__ bool pmex_fast_mesh(const PmeExArgs<float>& Xa, const PmeExDyn& dyn, double& e1, double& e2) {
+    constexpr int ORDER = 5;
+    const PmeArgs<float>& P = Xa.P;
+    const int X = 0, Y = PME_LDS_X, tw0 = PME_LDS_X + PME_LDS_Y, tw1 = tw0 + P.K[0], tw2 = tw1 + P.K[1];
+    const int AT = (tw2 + P.K[2] + 1) & ~1;
+    int4* at_i = reinterpret_cast<int4*>(pme_lds + AT); float4* at_f = reinterpret_cast<float4*>(pme_lds + AT + 2 * PMEX_LDS_ATOMS);
+    double* s_pot = reinterpret_cast<double*>(pme_lds + AT + 4 * PMEX_LDS_ATOMS);   // [PMEX_MAX_ALCH][8]: sums of (dw w w, w dw w, w w dw, w w w) phi_env, then of phi_alch
+    int* acc = reinterpret_cast<int*>(pme_lds + Y);
+    __shared__ int s_lo[2][3], s_hi[2][3], s_ref[3], s_first;
+    const int tid = threadIdx.x, n = P.n, n_sel = P.n_sel, ne = P.n_sel + Xa.n_alch;
+    const int K0 = P.K[0], K1 = P.K[1], K2 = P.K[2], Hz = K2 / 2 + 1;
+    const int ALCH = 1 << 30;   // flag in the cached atom index
+    if (ne > PMEX_LDS_ATOMS || Xa.n_alch > PMEX_MAX_ALCH || K0 * K1 * Hz > PME_LDS_Y || ne * 16 > PME_LDS_X || (ne * 48 + 1) / 2 > PME_LDS_Y) return false;
+    for (int k = tid; k < K0; k += PME_THREADS) pme_lds[tw0 + k] = make_float2(P.tw_cos[0][k], P.tw_sin[0][k]);
+    for (int k = tid; k < K1; k += PME_THREADS) pme_lds[tw1 + k] = make_float2(P.tw_cos[1][k], P.tw_sin[1][k]);
+    for (int k = tid; k < K2; k += PME_THREADS) pme_lds[tw2 + k] = make_float2(P.tw_cos[2][k], P.tw_sin[2][k]);
+    if (tid < 6) { s_lo[tid / 3][tid % 3] = 1 << 30; s_hi[tid / 3][tid % 3] = -(1 << 30); }
+    if (tid == 0) s_first = 1 << 30;
+    for (int k = tid; k < PMEX_MAX_ALCH * 8; k += PME_THREADS) s_pot[k] = 0.0;
+    __syncthreads();
+    for (int s = tid; s < ne; s += PME_THREADS) {
+        const int i = s < n_sel ? P.sel[s] : Xa.alch[s - n_sel];
+        int4 ti; float4 fr;
+        pme_locate(P, i, 0, ti.x, fr.x); pme_locate(P, i, 1, ti.y, fr.y); pme_locate(P, i, 2, ti.z, fr.z);
+        fr.w = (float)Xa.q[i]; ti.w = i | (Xa.alch_local[i] >= 0 ? ALCH : 0);
+        at_i[s] = ti; at_f[s] = fr;
+        int mine = fr.w != 0.0f ? s : (1 << 30);
+        for (int o = 32; o > 0; o >>= 1) mine = min(mine, __shfl_xor(mine, o, 64));
+        if ((tid & 63) == 0 && mine < (1 << 30)) atomicMin(&s_first, mine);
+    }
+    __syncthreads();
+    if (tid < 3) s_ref[tid] = s_first < ne ? (tid == 0 ? at_i[s_first].x : (tid == 1 ? at_i[s_first].y : at_i[s_first].z)) : 0;
+    __syncthreads();
+    {   // extents around the reference: [0] every charged entry (U), [1] the charged alchemical entries (A)
+        int lo[2][3], hi[2][3];
+        for (int r = 0; r < 2; r++) for (int d = 0; d < 3; d++) { lo[r][d] = 1 << 30; hi[r][d] = -(1 << 30); }
+        for (int s = tid; s < ne; s += PME_THREADS) {
+            if (at_f[s].w == 0.0f) continue;
+            const int4 ti = at_i[s];
+            const int tt[3] = {ti.x, ti.y, ti.z};
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                int del = tt[d] - s_ref[d]; const int K = P.K[d];
+                if (2 * del >= K) del -= K; else if (2 * del < -K) del += K;
+                lo[0][d] = min(lo[0][d], del); hi[0][d] = max(hi[0][d], del);
+                if (s >= n_sel) { lo[1][d] = min(lo[1][d], del); hi[1][d] = max(hi[1][d], del); }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                for (int o = 32; o > 0; o >>= 1) { lo[r][d] = min(lo[r][d], __shfl_xor(lo[r][d], o, 64)); hi[r][d] = max(hi[r][d], __shfl_xor(hi[r][d], o, 64)); }
+                if ((tid & 63) == 0) { atomicMin(&s_lo[r][d], lo[r][d]); atomicMax(&s_hi[r][d], hi[r][d]); }
+            }
+    }
+    __syncthreads();
+    PmeRegion R[2];   // [0] U, [1] A (inside U)
+    for (int r = 0; r < 2; r++) for (int d = 0; d < 3; d++) {
+        const int K = P.K[d];
+        if (s_hi[r][d] < s_lo[r][d]) { R[r].s[d] = 0; R[r].L[d] = 1; continue; }   // no charged atom: an empty block
+        R[r].L[d] = s_hi[r][d] - s_lo[r][d] + ORDER;
+        int st = (s_ref[d] + s_lo[r][d]) % K; if (st < 0) st += K;
+        R[r].s[d] = st;
+        if (R[r].L[d] >= K) { R[r].L[d] = K; R[r].s[d] = 0; }
+    }
+    {
+        const int Lx = R[0].L[0], Ly = R[0].L[1], Lz = R[0].L[2];   // (A's extents are at most U's)
+        if (!(Lx * Ly * Lz <= PME_LDS_X && Lx * K1 * Hz <= PME_LDS_X && Lx * Ly * Hz <= PME_LDS_Y)) return false;   // (block-uniform) a spread-out mobile set
+    }
+    float* wts = reinterpret_cast<float*>(pme_lds + X);   // spread: 32 floats per entry, w_x[8] w_y[8] w_z[8]
+    float* wg = reinterpret_cast<float*>(pme_lds + Y);    // gather: 48 floats per entry, w_x w_y w_z e_x e_y e_z (8 each)
+    // spread of one class (cls 0: the mobile environment, cls 1: the alchemical atoms) into the block Ri
+    auto spread = [&](int cls, const PmeRegion& Ri) {
+        const int sb = cls ? n_sel : 0, se = cls ? ne : n_sel, Ly = Ri.L[1], Lz = Ri.L[2];
+        for (int g = tid; g < Ri.L[0] * Ly * Lz; g += PME_THREADS) acc[g] = 0;
+        for (int s = sb + tid; s < se; s += PME_THREADS) {
+            const float4 fr = at_f[s];
+            float w0[ORDER], w1[ORDER], w2[ORDER], dw[ORDER];
+            pme_splines_c<float, ORDER>(fr.x, w0, dw); pme_splines_c<float, ORDER>(fr.y, w1, dw); pme_splines_c<float, ORDER>(fr.z, w2, dw);
+#pragma unroll
+            for (int k = 0; k < ORDER; k++) { wts[s * 32 + k] = w0[k]; wts[s * 32 + 8 + k] = w1[k]; wts[s * 32 + 16 + k] = w2[k]; }
+        }
+        __syncthreads();
+        const int per = ORDER * ORDER;
+        for (int w = tid; w < (se - sb) * per; w += PME_THREADS) {
+            const int s = sb + w / per, ab = w % per, a = ab / ORDER, b = ab - a * ORDER;
+            const float4 fr = at_f[s]; const int4 ti = at_i[s];
+            if (fr.w == 0.0f || (!cls && (ti.w & ALCH))) continue;   // (a mobile alchemical atom is spread with its class)
+            int ax = ti.x + a - Ri.s[0]; if (ax < 0) ax += K0; if (ax >= K0) ax -= K0;
+            int ay = ti.y + b - Ri.s[1]; if (ay < 0) ay += K1; if (ay >= K1) ay -= K1;
+            int az0 = ti.z - Ri.s[2]; if (az0 < 0) az0 += K2;
+            const float qab = fr.w * PME_FIX32 * wts[s * 32 + a] * wts[s * 32 + 8 + b];
+            const int row = (ax * Ly + ay) * Lz;
+#pragma unroll
+            for (int c = 0; c < ORDER; c++) {
+                int az = az0 + c; if (az >= K2) az -= K2;
+                atomicAdd(&acc[row + az], __float2int_rn(qab * wts[s * 32 + 16 + c]));
+            }
+        }
+        __syncthreads();
+    };
+    // the sums of one potential over the stencils of the entries [sb, se), from the block Ro in X (with_static: plus the frozen environment's mesh)
+    auto gather = [&](int sb, int se, const PmeRegion& Ro, bool with_static, auto&& sink) {
+        const int Ly = Ro.L[1], Lz = Ro.L[2];
+        for (int s = sb + tid; s < se; s += PME_THREADS) {
+            const float4 fr = at_f[s];
+            float w0[ORDER], w1[ORDER], w2[ORDER], e0[ORDER], e1_[ORDER], e2_[ORDER];
+            pme_splines_c<float, ORDER>(fr.x, w0, e0); pme_splines_c<float, ORDER>(fr.y, w1, e1_); pme_splines_c<float, ORDER>(fr.z, w2, e2_);
+            float* wv = wg + (s - sb) * 48;
+#pragma unroll
+            for (int k = 0; k < ORDER; k++) { wv[k] = w0[k]; wv[8 + k] = w1[k]; wv[16 + k] = w2[k]; wv[24 + k] = e0[k]; wv[32 + k] = e1_[k]; wv[40 + k] = e2_[k]; }
+        }
+        __syncthreads();
+        for (int s0 = sb + (tid >> 5); s0 < se; s0 += PME_THREADS / 32) {
+            const int ab = tid & 31;
+            const float4 fr = at_f[s0]; const int4 ti = at_i[s0];
+            float fx = 0.0f, fy = 0.0f, fz = 0.0f, fv = 0.0f;
+            if (fr.w != 0.0f && ab < ORDER * ORDER) {
+                const int a = ab / ORDER, b = ab - a * ORDER;
+                const float* wv = wg + (s0 - sb) * 48;
+                int ix = ti.x + a; if (ix >= K0) ix -= K0;
+                int iy = ti.y + b; if (iy >= K1) iy -= K1;
+                int ax = ix - Ro.s[0]; if (ax < 0) ax += K0;
+                int ay = iy - Ro.s[1]; if (ay < 0) ay += K1;
+                int az0 = ti.z - Ro.s[2]; if (az0 < 0) az0 += K2;
+                const int row = (ax * Ly + ay) * Lz;
+                float sx = 0.0f, sz = 0.0f;
+#pragma unroll
+                for (int c = 0; c < ORDER; c++) {
+                    int az = az0 + c; if (az >= K2) az -= K2;
+                    float phi = pme_lds[X + row + az].x;
+                    if (with_static) { int iz = ti.z + c; if (iz >= K2) iz -= K2; phi += P.phi_f[((size_t)ix * K1 + iy) * K2 + iz]; }
+                    sx = fmaf(wv[16 + c], phi, sx); sz = fmaf(wv[40 + c], phi, sz);
+                }
+                fx = wv[24 + a] * wv[8 + b] * sx; fy = wv[a] * wv[32 + b] * sx; fz = wv[a] * wv[8 + b] * sz; fv = wv[a] * wv[8 + b] * sx;
+            }
+            double g[4] = {(double)fx, (double)fy, (double)fz, (double)fv};   // fixed-order sum over the 32 lanes of the atom
+            for (int o = 16; o > 0; o >>= 1) { g[0] += __shfl_xor(g[0], o, 64); g[1] += __shfl_xor(g[1], o, 64); g[2] += __shfl_xor(g[2], o, 64); g[3] += __shfl_xor(g[3], o, 64); }
+            if ((tid & 31) == 0) sink(s0, ti.w & ~ALCH, (ti.w & ALCH) != 0, g);
+        }
+        __syncthreads();
+    };
+    // ---- 1. the mobile environment: U in, A out; phi_env (mobile + frozen) at the alchemical atoms
+    spread(0, R[0]);
+    pmex_fast_pipeline(P, R[0], R[1]);
+    gather(n_sel, ne, R[1], P.have_static != 0, [&](int, int i, bool, const double* g) {
+        double* sp = s_pot + 8 * Xa.alch_local[i];
+        sp[0] = g[0]; sp[1] = g[1]; sp[2] = g[2]; sp[3] = g[3];
+    });
+    // ---- 2. the alchemical atoms: A in, U out; phi_alch at every entry, the per-slot forces of the mobile atoms
+    spread(1, R[1]);
+    pmex_fast_pipeline(P, R[1], R[0]);
+    gather(0, ne, R[0], false, [&](int s, int i, bool alch, const double* g) {
+        if (s >= n_sel) { double* sp = s_pot + 8 * Xa.alch_local[i] + 4; sp[0] = g[0]; sp[1] = g[1]; sp[2] = g[2]; sp[3] = g[3]; return; }
+        const double q = Xa.q[i];
+        const double sc[3] = {-q * K0 * P.box.invL[0], -q * K1 * P.box.invL[1], -q * K2 * P.box.invL[2]};
+        const double* sp = s_pot + 8 * (alch ? Xa.alch_local[i] : 0);
+        double fe[3], fa[3];
+        for (int k = 0; k < 3; k++) { fe[k] = alch ? sc[k] * sp[k] : 0.0; fa[k] = sc[k] * g[k]; }
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            const double le = dyn.le[sl];
+            for (int k = 0; k < 3; k++) Xa.fex[(size_t)(sl * 3 + k) * n + i] = alch ? le * (fe[k] + le * fa[k]) : le * fa[k];
+        }
+    });
+    // ---- energies of the alchemical charges in the two potentials: lane a of wave 0 holds atom a's
+    e1 = 0.0; e2 = 0.0;
+    if (tid < Xa.n_alch) {
+        const int i = Xa.alch[tid];
+        const double q = Xa.q[i];
+        const double* sp = s_pot + 8 * Xa.alch_local[i];
+        e1 = q * sp[3]; e2 = 0.5 * q * sp[7];
+    }
+    return true;
+}
+
+// FAST: the mesh part was served by pmex_fast_mesh (its forces are in fex, e1 / e2 hold the alchemical atoms' mesh energies per lane)
+template <typename T, bool FAST = false>
+__device__ __forceinline__ void pmex_body(const PmeExArgs<T>& X, const PmeExDyn& dyn, double e1_in = 0.0, double e2_in = 0.0) {
+    constexpr int ORDER = 5;
+    const PmeArgs<T>& P = X.P;
+    const int tid = threadIdx.x;
+    const int K0 = P.K[0], K1 = P.K[1], K2 = P.K[2], n = P.n;
+    __shared__ double s_e[PME_THREADS / 64][3];
+    // ---- the two charge meshes in fixed point
+    if constexpr (!FAST) {
+    for (int g = tid; g < P.ng; g += PME_THREADS) { P.acc[g] = 0ull; X.acc2[g] = 0ull; }
+    __syncthreads();
+    {
+        const int per = ORDER * ORDER;
+        const long total = (long)(P.n_sel + X.n_alch) * per;
+        for (long w = tid; w < total; w += PME_THREADS) {
+            const int s = (int)(w / per), ab = (int)(w - (long)s * per), a = ab / ORDER, b = ab - a * ORDER;
+            const bool alch = s >= P.n_sel;
+            const int i = alch ? X.alch[s - P.n_sel] : P.sel[s];
+            const double q = alch ? X.q[i] : P.qn[i];
+            if (q == 0.0) continue;
+            unsigned long long* acc = alch ? X.acc2 : P.acc;
+            int t0, t1, t2; T d0, d1, d2;
+            pme_locate(P, i, 0, t0, d0); pme_locate(P, i, 1, t1, d1); pme_locate(P, i, 2, t2, d2);
+            T w0[ORDER], w1[ORDER], w2[ORDER], dw[ORDER];
+            pme_splines_c<T, ORDER>(d0, w0, dw); pme_splines_c<T, ORDER>(d1, w1, dw); pme_splines_c<T, ORDER>(d2, w2, dw);
+            T wa = (T)0, wb = (T)0;
+#pragma unroll
+            for (int k = 0; k < ORDER; k++) { if (k == a) wa = w0[k]; if (k == b) wb = w1[k]; }
+            int ix = t0 + a; if (ix >= K0) ix -= K0;
+            int iy = t1 + b; if (iy >= K1) iy -= K1;
+            const double qab = q * (double)wa * (double)wb;
+#pragma unroll
+            for (int c = 0; c < ORDER; c++) {
+                int iz = t2 + c; if (iz >= K2) iz -= K2;
+                const long long v = llrint(qab * (double)w2[c] * PME_FIX);
+                atomicAdd(&acc[((size_t)ix * K1 + iy) * K2 + iz], (unsigned long long)v);
+            }
+        }
+    }
+    __syncthreads();
+    for (int g = tid; g < P.ng; g += PME_THREADS) {
+        P.a_re[g] = (T)((double)(long long)P.acc[g] * (1.0 / PME_FIX));
+        P.a_im[g] = (T)((double)(long long)X.acc2[g] * (1.0 / PME_FIX));
+    }
+    __syncthreads();
+    // ---- forward z, y, x; eterm; backward x, y, z: real part = potential of the mobile environment, imaginary part = of the alchemical atoms
+    pme_dft_axis(P, P.a_re, P.a_im, P.b_re, P.b_im, 2, (T)-1); __syncthreads();
+    pme_dft_axis(P, P.b_re, P.b_im, P.a_re, P.a_im, 1, (T)-1); __syncthreads();
+    pme_dft_axis(P, P.a_re, P.a_im, P.b_re, P.b_im, 0, (T)-1); __syncthreads();
+    for (int g = tid; g < P.ng; g += PME_THREADS) { const T et = P.eterm[g]; P.b_re[g] *= et; P.b_im[g] *= et; }
+    __syncthreads();
+    pme_dft_axis(P, P.b_re, P.b_im, P.a_re, P.a_im, 0, (T)1); __syncthreads();
+    pme_dft_axis(P, P.a_re, P.a_im, P.b_re, P.b_im, 1, (T)1); __syncthreads();
+    pme_dft_axis(P, P.b_re, P.b_im, P.a_re, P.a_im, 2, (T)1); __syncthreads();
+    }
+    // ---- energies: the alchemical atoms' charges in the two potentials (wave 0; at most 64 alchemical atoms), then the correction pairs
+    double e1 = e1_in, e2 = e2_in, caa = 0.0;
+    if (tid < X.n_alch) {
+        const int i = X.alch[tid];
+        const double q = X.q[i];
+        if (!FAST && q != 0.0) {
+            double env[4], alc[4];
+            pmex_gather(P, i, true, env, alc);
+            e1 = q * env[3]; e2 = 0.5 * q * alc[3];
+        }
+        if (X.mobile_index[i] < 0) for (int k = 0; k < 9; k++) X.fex[(size_t)k * n + i] = 0.0;   // (a frozen alchemical atom: k_finalize reads its row)
+    }
+    for (int p = tid; p < X.n_pair; p += PME_THREADS) {
+        double d[3], fs;
+        const int kind = X.pair_kind[p];
+        const double e = pmex_pair(X, X.pair_i[p], X.pair_j[p], X.pair_qq[p], kind, d, &fs);
+        if (kind == 0) e1 += e; else if (kind == 1) e2 += e; else caa += e;
+    }
+    e1 = wave_sum(e1); e2 = wave_sum(e2); caa = wave_sum(caa);
+    if ((tid & 63) == 0) { s_e[tid >> 6][0] = e1; s_e[tid >> 6][1] = e2; s_e[tid >> 6][2] = caa; }
+    // ---- forces of the mesh on the mobile atoms, per slot
+    if constexpr (!FAST) for (int s = tid; s < P.n_sel; s += PME_THREADS) {
+        const int i = P.sel[s];
+        const bool alch = X.alch_local[i] >= 0;
+        const double q = X.q[i];
+        double fe[3] = {0.0, 0.0, 0.0}, fa[3] = {0.0, 0.0, 0.0};
+        if (q != 0.0) {
+            double env[4], alc[4];
+            pmex_gather(P, i, alch, env, alc);
+            const double sc[3] = {-q * K0 * P.box.invL[0], -q * K1 * P.box.invL[1], -q * K2 * P.box.invL[2]};
+            for (int k = 0; k < 3; k++) { fe[k] = sc[k] * env[k]; fa[k] = sc[k] * alc[k]; }
+        }
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            const double le = dyn.le[sl];
+            for (int k = 0; k < 3; k++) X.fex[(size_t)(sl * 3 + k) * n + i] = alch ? le * (fe[k] + le * fa[k]) : le * fa[k];
+        }
+    }
+    __syncthreads();
+    // ---- forces of the correction pairs: one thread per mobile atom that has any, its entries in list order
+    for (int r = tid; r < X.n_row; r += PME_THREADS) {
+        const int i = X.row_atom[r];
+        double f1[3] = {0.0, 0.0, 0.0}, f2[3] = {0.0, 0.0, 0.0};
+        for (int e = X.row_start[r]; e < X.row_start[r + 1]; e++) {
+            double d[3], fs;
+            const int kind = X.ent_kind[e];
+            pmex_pair(X, i, X.ent_j[e], X.ent_qq[e], kind, d, &fs);
+            for (int k = 0; k < 3; k++) {
+                const double f = fs * d[k];
+                if (kind == 0) f1[k] += f; else if (kind == 1) f2[k] += f; else { f2[k] += f; f1[k] -= f; }
+            }
+        }
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            const double le = dyn.le[sl];
+            for (int k = 0; k < 3; k++) X.fex[(size_t)(sl * 3 + k) * n + i] += le * (f1[k] + le * f2[k]);
+        }
+    }
+    if (tid == 0) {
+        double t1 = 0.0, t2 = 0.0, tc = 0.0;
+        for (int w = 0; w < PME_THREADS / 64; w++) { t1 += s_e[w][0]; t2 += s_e[w][1]; tc += s_e[w][2]; }
+        if (X.path) X.path[FAST ? 0 : 1]++;   // (read by blues_get_exact_pme_path: which mesh path served the alchemical class)
+        X.epart[0] = 0.0; X.epart[1] = t1 + X.c1; X.epart[2] = t2 + X.c2 + tc; X.epart[3] = 0.0; X.epart[4] = -tc; X.epart[5] = tc;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(PME_THREADS) k_pme_exact_b(const PmeExArgs<T>* __restrict__ recs, PmeExDyn dyn) {
+    const PmeExArgs<T>& X = recs[blockIdx.x];
+    if (!X.active) return;
+    pmex_body<T>(X, dyn);
+}
+
+// mixed precision on a mesh whose half spectrum fits LDS: the pruned pipeline, with the general body (kept out of line, out of this
+// kernel's register allocation) for members whose atoms or blocks do not fit
+__device__ __noinline__ void pmex_body_general_f(const PmeExArgs<float>& X, const PmeExDyn& dyn) { pmex_body<float, false>(X, dyn); }
+__global__ void __launch_bounds__(PME_THREADS) k_pme_exact_fast_b(const PmeExArgs<float>* __restrict__ recs, PmeExDyn dyn) {
+    const PmeExArgs<float>& X = recs[blockIdx.x];
+    if (!X.active) return;
+    double e1, e2;
+    if (!pmex_fast_mesh(X, dyn, e1, e2)) { pmex_body_general_f(X, dyn); return; }
+    pmex_body<float, true>(X, dyn, e1, e2);
+}

@@ -25,13 +25,24 @@ class NativeEngine:
         try:
             system.check_custom_forces()
             system.check_implicit_solvent(integrator)
+            system.check_alchemical_pme_treatment(integrator)
         except ValueError as e:
             raise EngineError(str(e))
         self._lib = load()
         sd, self._keep_s = system.to_desc()
         idesc, self._keep_i = integrator.to_desc()
         h = C.c_void_p()
-        if system.implicit_solvent is not None:
+        ext = system.ext_desc()
+        if ext is not None:
+            # (additive entry point: a library built before it loads, and only a System that needs it says so)
+            if not hasattr(self._lib, "blues_engine_create_ext"):
+                raise EngineError("alchemical_pme_treatment %r needs blues_engine_create_ext, which this library does not have: rebuild it "
+                                  "(python -m blues_amd.build)" % (system.alchemical_pme_treatment,))
+            gd = None
+            if system.implicit_solvent is not None:
+                gd, self._keep_g = system.implicit_solvent.to_desc()
+            rc = self._lib.blues_engine_create_ext(C.byref(sd), C.byref(idesc), C.byref(gd) if gd is not None else None, C.byref(ext), int(device), C.byref(h))
+        elif system.implicit_solvent is not None:
             gd, self._keep_g = system.implicit_solvent.to_desc()
             rc = self._lib.blues_engine_create_gb(C.byref(sd), C.byref(idesc), C.byref(gd), int(device), C.byref(h))
         else:
@@ -195,7 +206,11 @@ class NativeEngine:
 
     def stats(self):
         s = (C.c_int64 * _abi.N_STATS)(); self._check(self._lib.blues_get_stats(self._h, s))
-        return {"force_passes": s[0], "list_generation": s[1], "kernel_launches": s[2], "i_tiles": s[3],
+        path = (C.c_int64 * 2)()   # (exact PME treatment: launches of its mesh kernel by path; a library without the entry has no such engines)
+        if hasattr(self._lib, "blues_get_exact_pme_path"):
+            self._check(self._lib.blues_get_exact_pme_path(self._h, path))
+        return {"exact_pme_fast_launches": int(path[0]), "exact_pme_general_launches": int(path[1]),
+                "force_passes": s[0], "list_generation": s[1], "kernel_launches": s[2], "i_tiles": s[3],
                 "clusters": s[4], "jcap": s[5], "npart": s[6], "seg_len": s[7] // 1000, "wpb": s[7] % 1000,
                 "max_jcount": s[8], "resorts": s[9], "list_builds": s[10], "own_energy_evaluations": s[11],
                 "nonbonded_kernel": s[12], "tiles_per_list": s[13], "atom_list_entries": s[14], "atom_list_iterations": s[15],
@@ -214,7 +229,7 @@ class NativeEngine:
 
 def _minimize_desc(lib, fire):
     """BluesMinimizeDesc from keyword overrides (None: the library's defaults); EngineError when the library has no minimiser."""
-    missing = [name for name in _abi.OPTIONAL_SYMBOLS if not hasattr(lib, name)]
+    missing = [name for name in _abi.MINIMIZE_SYMBOLS if not hasattr(lib, name)]
     if missing:
         raise EngineError("the engine library lacks %s: it was built before the device-resident minimiser; rebuild it "
                           "(python -m blues_amd.build)" % ", ".join(missing))

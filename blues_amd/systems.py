@@ -29,6 +29,8 @@ def save_system(path, system: SystemData, **extra):
     d = {k: np.asarray(getattr(system, k)) for k in _ARRAY_FIELDS if getattr(system, k) is not None}
     d.update({k: np.asarray(getattr(system, k)) for k in _SCALAR_FIELDS + _OPTIONAL_SCALARS})
     d["pme_grid"] = np.asarray(system.pme_grid, dtype=np.int32)
+    if system.alchemical_pme_treatment != "direct-space":   # (the default is not written: files stay readable by earlier versions)
+        d["alchemical_pme_treatment"] = np.asarray(system.alchemical_pme_treatment)
     if system.implicit_solvent is not None:
         d.update({"gb_" + k: np.asarray(getattr(system.implicit_solvent, k)) for k in _GB_FIELDS})
     d.update({k: np.asarray(v) for k, v in extra.items()})
@@ -49,6 +51,8 @@ def load_system(path):
     if "gb_model" in z.files:
         kw["implicit_solvent"] = ImplicitSolventData(int(z["gb_model"]), z["gb_radius"], z["gb_scale"], float(z["gb_solute_dielectric"]),
                                                      float(z["gb_solvent_dielectric"]), float(z["gb_surface_area_energy"]))
+    if "alchemical_pme_treatment" in z.files:   # (older files: "direct-space", the field's default)
+        kw["alchemical_pme_treatment"] = str(z["alchemical_pme_treatment"].item())
     extra = {k: z[k] for k in z.files if k not in kw and not k.startswith("gb_")}
     return SystemData(**kw), extra
 
@@ -74,6 +78,17 @@ def with_reciprocal_space(system: SystemData, dispersion_correction=True):
     s.pme_grid = pme_grid_for(system.box, system.ewald_alpha, system.cutoff)
     s.pme_order = 5
     s.dispersion_correction = bool(dispersion_correction)
+    return s
+
+
+def with_alchemical_pme_treatment(system: SystemData, treatment):
+    """The same System with openmmtools' alchemical_pme_treatment (SystemFactory.generateAlchSystem, reference blues/simulation.py:236,
+    274-284) set to "direct-space" or "exact"; anything else ('coulomb' included) raises ValueError."""
+    from ._abi import alchemical_pme_treatment_code
+    alchemical_pme_treatment_code(treatment)
+    s = copy.copy(system)
+    s.alchemical_pme_treatment = treatment
+    s.check_alchemical_pme_treatment()
     return s
 
 
@@ -173,6 +188,7 @@ def tile_system(system: SystemData, reps):
         residue_of_atom=None if res is None else np.concatenate([res + c * nres for c in range(ncopy)]).astype(np.int32),
         names=None if system.names is None else list(system.names) * ncopy,
         implicit_solvent=None if system.implicit_solvent is None else system.implicit_solvent.subset(np.tile(np.arange(n), ncopy)),
+        alchemical_pme_treatment=system.alchemical_pme_treatment,
     )
 
 
@@ -287,7 +303,7 @@ def assemble_s23k_solute(base: SystemData, vel, removed_waters, inserted_x, inse
         alchemical_atoms=np.arange(n_lig, dtype=np.int32), nonbonded_method=base.nonbonded_method, cutoff=base.cutoff, ewald_alpha=base.ewald_alpha,
         softcore_alpha=base.softcore_alpha, annihilate_electrostatics=base.annihilate_electrostatics, annihilate_sterics=base.annihilate_sterics,
         remove_cm_motion=base.remove_cm_motion, pme_order=base.pme_order, dispersion_correction=base.dispersion_correction, positions=pos,
-        residue_of_atom=new_res.astype(np.int32))
+        residue_of_atom=new_res.astype(np.int32), alchemical_pme_treatment=base.alchemical_pme_treatment)
     assert s.n_atoms == n
     return s, v
 
@@ -355,7 +371,7 @@ def alchemical_difference_plan(alchemical: SystemData, plain: SystemData):
      and every direct-space term cancels.  What is left:
       * nothing, without reciprocal space ({"kind": "zero"});
       * with PME ('direct-space' alchemical treatment: the alchemical atoms' charges stay out of the mesh, the self term and the
-        excluded-pair corrections, their epsilons out of the dispersion correction): the mesh energy with every atom's charge minus the
+        excluded-pair corrections, their epsilons out of the dispersion correction; for the 'exact' treatment see below): the mesh energy with every atom's charge minus the
         mesh energy with the alchemical charges at 0 (the engine: blues_mesh_energy), the erf corrections of the excluded pairs that
         hold an alchemical atom (a handful of intra-ligand pairs: host arithmetic), and three constants of the box.
     Returns None when the Systems differ in anything else: the four energies of the reference's formula are evaluated then."""
@@ -378,6 +394,15 @@ def alchemical_difference_plan(alchemical: SystemData, plain: SystemData):
     if tuple(alchemical.pme_grid) != tuple(plain.pme_grid) or getattr(alchemical, "barostat", None) or getattr(plain, "barostat", None):
         return None
     lig = np.asarray(alchemical.alchemical_atoms, dtype=np.int64)
+    if alchemical.alchemical_pme_treatment == "exact":
+        # 'exact' treatment: every electrostatic term of the NCMC System uses q~ = lambda_electrostatics q, so at lambda = (1, 1) its
+        # reciprocal space, self term, background and excluded-pair corrections ARE the plain System's.  D is a constant of the box
+        # (the alchemical atoms' share of the dispersion correction) and D(x0) - D(x1) = 0 at the switch's fixed box: no mesh launches,
+        # no host erf arithmetic -- the drivers treat it as the "zero" kind.
+        const = 0.0
+        if alchemical.dispersion_correction:
+            const = dispersion_correction_energy(alchemical) - dispersion_correction_energy(alchemical, zero_epsilon=lig)
+        return {"kind": "zero", "treatment": "exact", "const": float(const)}
     q = np.asarray(alchemical.charge, dtype=np.float64)
     is_lig = np.zeros(alchemical.n_atoms, bool); is_lig[lig] = True
     pairs = set()

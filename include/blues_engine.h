@@ -196,6 +196,29 @@ typedef struct BluesImplicitSolventDesc {
 } BluesImplicitSolventDesc;
 /* gb = NULL (or model BLUES_GB_NONE): blues_engine_create */
 int blues_engine_create_gb(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, const BluesImplicitSolventDesc *gb, int device, BluesEngine **out);
+
+/* How full PME (BLUES_NB_PME) treats the alchemical atoms' charges: openmmtools' alchemical_pme_treatment, as
+ * SystemFactory.generateAlchSystem passes it on (reference blues/simulation.py:236, 274-284, 300-302).  Additive to ABI 9: neither
+ * descriptor above changes; a library without this entry loads, and only a caller that asks for the exact treatment needs it.
+ *   BLUES_ALCH_PME_DIRECT_SPACE  the alchemical charges stay out of the mesh, the self term and the excluded-pair corrections
+ *                                (what blues_engine_create does);
+ *   BLUES_ALCH_PME_EXACT         every electrostatic term uses q~ = lambda_electrostatics q for an alchemical atom: reciprocal space,
+ *                                self term, neutralising background and the erf corrections of excluded pairs are
+ *                                E0 + le E1 + le^2 E2; non-exception alchemical x alchemical direct-space pairs take le^2, exceptions
+ *                                keep le (recalled from openmmtools' AbsoluteAlchemicalFactory, not source-pinned).  Energy term [8]
+ *                                is then the whole reciprocal-space group evaluated with q~.
+ * Creation fails, with the reason, for the exact treatment on anything but BLUES_NB_PME, with annihilate_electrostatics = 0, with
+ * measure_shadow_work / measure_heat (the ledger's device-side energy sum does not know the new partials) and with a
+ * switching_mode integrator; blues_mesh_energy refuses such an engine (its System at lambda = (1, 1) differs from the plain one
+ * by box constants only: there is no mesh differential to take).  A batch may not mix treatments. */
+#define BLUES_ALCH_PME_DIRECT_SPACE 0
+#define BLUES_ALCH_PME_EXACT 1
+typedef struct BluesSystemExt {
+    int32_t struct_size;                 /* sizeof(BluesSystemExt) of the caller */
+    int32_t alchemical_pme_treatment;    /* BLUES_ALCH_PME_* */
+} BluesSystemExt;
+/* ext = NULL: blues_engine_create_gb */
+int blues_engine_create_ext(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, const BluesImplicitSolventDesc *gb, const BluesSystemExt *ext, int device, BluesEngine **out);
 int blues_engine_destroy(BluesEngine *h);
 const char *blues_last_error(const BluesEngine *h);
 int blues_abi_version(void);
@@ -359,6 +382,10 @@ int blues_reset(BluesEngine *h);
  * [21] threads per block of the step kernel (BluesTuning.pack_clusters) */
 #define BLUES_N_STATS 22
 int blues_get_stats(BluesEngine *h, int64_t stats[BLUES_N_STATS]);
+/* alchemical_pme_treatment "exact": launches of the alchemical class's mesh kernel so far, counted on the device by the path that
+ * served them: [0] the pruned in-LDS pipeline (mixed precision, mesh and atoms fit), [1] the general one.  Zeros for any other engine.
+ * Additive (BLUES_ABI_VERSION unchanged). */
+int blues_get_exact_pme_path(BluesEngine *h, int64_t out[2]);
 /* time `reps` launches of the dominant nonbonded kernel alone with HIP events
  * on the engine's own stream; returns mean microseconds per launch. */
 int blues_time_nonbonded(BluesEngine *h, int32_t reps, double *usec_per_launch);
