@@ -324,6 +324,9 @@ struct BluesEngine {
     DBuf<unsigned short> d_alist, d_plist; DBuf<int> d_acount, d_pcount, d_pneed; DBuf<unsigned> d_xprune[3];   // pruned lists (by i-slot)
     DBuf<uint4> d_pimg4; DBuf<float2> d_pimg2; DBuf<int> d_mlist, d_mcount; int mcap = 0;   // packed group images (ListArgs)
     DBuf<unsigned short> d_aself; DBuf<uint4> d_pimgb; DBuf<int> d_sx_row;
+    // kept superset of every group list's candidates (kernels_nb.h: build_lists_body): buffers sized by the layout; sup_slack: ListArgs.sup_slack
+    // (nm; <= 0: every rebuild scans all atoms).  Development switch: blues_set_global "group_list_superset"
+    DBuf<int> d_sup, d_sup_stat; DBuf<SupHdr> d_sup_hdr; int sup_cap = 0; float sup_slack = 0.3f;
     float alist_pf_reach = 0.8f;   // ListArgs.pf_reach (nm): the reach up to which a wave of the atoms'-list builder prefilters its group's list; < 0: never.  Development switch: blues_set_global "atom_list_prefilter"
     int n_entries = 0;
     int int_blocks = 1, int_threads = 128;
@@ -1306,8 +1309,14 @@ static int sort_and_tile(BluesEngine* h) {
         // list -- without laying anybody out again: reshape_groups; 1.5 MB per member of the benchmark system)
         h->lists_alloc = h->k1_mode == 2 ? std::max(1, h->n_itiles) : 0;
         const int nt_alloc = h->k1_mode == 2 ? h->lists_alloc + 1 : nt;
-        h->d_jlist.alloc((size_t)nt_alloc * jcap); h->d_jstage.alloc((size_t)nt_alloc * LIST_WAVES * ((((n + LIST_WAVES - 1) / LIST_WAVES) + 63) & ~63)); h->d_jcount.alloc(nt_alloc); h->d_batch_slot.alloc((size_t)nt_alloc * (jcap / 64));
+        h->d_jlist.alloc((size_t)nt_alloc * jcap); h->d_jstage.alloc((size_t)(h->sup_slack > 0.0f ? 2 : 1) * nt_alloc * LIST_WAVES * ((((n + LIST_WAVES - 1) / LIST_WAVES) + 63) & ~63)); h->d_jcount.alloc(nt_alloc); h->d_batch_slot.alloc((size_t)nt_alloc * (jcap / 64));
         h->d_mask_pool.alloc((size_t)nt_alloc * MASK_QUOTA * 64);
+        // (the lists' kept supersets: at most half the atoms each -- a larger one is never valid; the headers start as "none yet", and the
+        // forced rebuild that follows every layout derives them for the new sorted order.  Device memory per member of the benchmark
+        // system, with room for the finest shape like the lists themselves: 281 KB of supersets and, above, 565 KB for the second half of
+        // jstage that a derivation stages through -- 0.85 MB on the member's 25 MB)
+        h->sup_cap = h->sup_slack > 0.0f ? ((n / 2) + 63) & ~63 : 0;
+        if (h->sup_cap) { h->d_sup.reserve((size_t)nt_alloc * h->sup_cap); h->d_sup_hdr.alloc(nt_alloc); if (!h->d_sup_stat.p) h->d_sup_stat.alloc(2); }   // (the two counts live as long as the engine)
         h->d_fpart.alloc((size_t)h->npart * 3 * h->n_islots);
         if (h->k1_mode == 2) {
             h->d_alist.alloc((size_t)h->n_islots * h->acap); h->d_acount.alloc(h->n_islots); h->d_aself.alloc(h->n_islots);
@@ -1541,7 +1550,8 @@ static ListArgs make_list_args(BluesEngine* h) {
     a.tile_atoms = h->d_tile_atoms.p; a.jlist = h->d_jlist.p; a.jstage = h->d_jstage.p; a.jcount = h->d_jcount.p; a.batch_slot = h->d_batch_slot.p;
     a.mask_pool = h->d_mask_pool.p; a.batch_req = batch_req_ptr(h); a.ex_start = h->d_ex_start.p; a.ex_idx = h->d_ex_idx.p; a.flags = h->d_flags.p;
     for (int k = 0; k < 3; k++) { a.x[k] = h->d_x[k].p; a.xbuild[k] = h->d_xbuild[k].p; }
-    a.fJ = h->d_fJ.p; a.n_fJ = 9 * h->n;
+    if (h->sup_cap > 0 && h->d_sup_stat.p) { a.sup = h->d_sup.p; a.sup_hdr = h->d_sup_hdr.p; a.sup_cap = h->sup_cap; a.sup_slack = h->sup_slack; a.sup_stat = h->d_sup_stat.p; }   // (switched off with buffers there: sup_slack 0)
+    a.fJ = h->d_fJ.p; a.mob_atoms = h->d_mobile_atoms.p; a.sorted_of_orig = h->d_sorted_of_orig.p; a.n_mob = (int)h->mobile.size();
     a.alch_jrec = h->alch.empty() ? nullptr : (void*)h->d_jrec.p; a.p_sigma = h->d_sigma.p; a.p_eps = h->d_eps.p; a.p_charge = h->d_charge.p;
     if (h->k1_mode == 2) { a.alist = h->d_alist.p; a.acount = h->d_acount.p; a.acap = h->acap; }
     a.S = h->S; a.n_lists = h->n_lists; a.hint_count = h->hint_count; a.no_sphere = h->tune.no_sphere;
@@ -4344,6 +4354,14 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
     else if (k == "n_lambda_steps") *value = h->n_lambda;
     else if (k == "nsteps") *value = h->nsteps;
     else if (k == "protocol_work") { if (read_acc(h, &a)) return 1; *value = a.protocol_work; }
+    else if (k == "group_list_superset_served" || k == "group_list_superset_fallback") {
+        // rebuilds of this engine in which group list 0 was served from its kept superset / scanned every atom (both 0 with the switch off)
+        int st[2] = {0, 0};
+        if (flush_program(h)) return 1;
+        HIP_OK(h, hipStreamSynchronize(h->stream));
+        if (h->d_sup_stat.p) HIP_OK(h, hipMemcpy(st, h->d_sup_stat.p, sizeof st, hipMemcpyDeviceToHost));   // (no layout has made room for supersets yet: 0, 0)
+        *value = st[k == "group_list_superset_served" ? 0 : 1];
+    }
     else if (k == "shadow_work") {
         if (h->switch_mode != BLUES_SWITCH_NONE) *value = h->sw_shadow;
         else if (h->led_flags & LED_SHADOW) { if (read_acc(h, &a)) return 1; *value = a.shadow_work; }
@@ -4383,6 +4401,12 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
 int blues_set_global(BluesEngine* h, const char* name, double value) {
     HIP_OK(h, hipSetDevice(h->device));
     std::string k(name);
+    // development switch of the group lists' kept supersets (kernels_nb.h: build_lists_body), not an integrator variable: 0: every rebuild
+    // scans all atoms; N > 0: a superset reaches N picometres beyond its list's sphere (default 300).  The lists are the same either way.
+    // The buffers are sized by a layout that finds the switch on: where the last layout found it off, N > 0 takes effect with the next
+    // one.  While it is off with buffers there, every rebuild the host forces still marks the kept headers "none yet", so turning it
+    // on again finds nothing older than the last change from outside.  The Python loader maps BLUES_GROUP_LIST_SUPERSET onto it at creation
+    if (k == "group_list_superset") { if (flush_program(h)) return 1; h->sup_slack = value <= 0.0 ? 0.0f : (float)(std::min(value, 1e5) * 1e-3); h->args_epoch++; return 0; }
     // development switch of the atoms'-list builder (kernels_nb.h: build_atom_lists_body), not an integrator variable: 0: every wave
     // takes the direct walk; N > 0: waves whose atoms lie within N picometres of their centre prefilter their group's list (default
     // 800: scripts/census_atom_list_prefilter.py).  The lists are the same either way; the Python loader maps BLUES_ATOM_LIST_PREFILTER onto it
@@ -4526,7 +4550,7 @@ int blues_time_list_build(BluesEngine* h, int32_t reps, double* usec) {
     if (rc) return 1;
     if (ensure_timing(h)) return 1;
     HIP_OK(h, hipEventRecord(h->ev0, h->stream));
-    for (int r = 0; r < reps && !rc; r++) rc = launch_lists_p(h, 1);
+    for (int r = 0; r < reps && !rc; r++) rc = launch_lists_p(h, 2);   // (2: rebuild whatever the displacement says, as a chain's own request would -- the kept supersets count, kernels_nb.h)
     if (rc) return 1;
     HIP_OK(h, hipEventRecord(h->ev1, h->stream));
     HIP_OK(h, hipEventSynchronize(h->ev1));
@@ -4537,6 +4561,7 @@ int blues_time_list_build(BluesEngine* h, int32_t reps, double* usec) {
 #ifdef BLUES_STAMP
     { long long st[32]; hipMemcpyFromSymbol(st, HIP_SYMBOL(g_nb_stamps), sizeof st);
       fprintf(stderr, "[stamps] group lists, block 0 (cycles since its start; box+sphere, scan, barrier, concatenated+counts, image packed):"); for (int i = 1; i < 5; i++) fprintf(stderr, " %lld", st[i] - st[0]); fprintf(stderr, " %lld\n", st[9] - st[0]);
+      fprintf(stderr, "[stamps] alchemical tile's block (cycles since its start; scanned, records written): %lld %lld | helper block 0 (cycles from its start to its end): %lld\n", st[12] - st[11], st[13] - st[11], st[15] - st[14]);   // (each block against its own first stamp: the counters of two XCDs are unrelated)
       fprintf(stderr, "[stamps] atoms' lists, block 0 (cycles since its start; bitmap, exclusions found, walk, counts written):"); for (int i = 6; i < 9; i++) fprintf(stderr, " %lld", st[i] - st[5]); fprintf(stderr, " %lld | between the two kernels' starts %lld\n", st[10] - st[5], st[5] - st[0]); }
 #endif
     return check_flags(h);

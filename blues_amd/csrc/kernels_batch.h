@@ -101,8 +101,7 @@ __global__ void __launch_bounds__(LIST_THREADS) k_build_lists_b(const RepNb<R>* 
     for (int i = blockIdx.x; i < nact * bpc; i += gridDim.x) {
         const int m = i / bpc;
         const RepNb<R>& rp = reps[work[1 + m]];
-        const ListArgs a = rp.L; const NbConst<R> c = rp.c;
-        build_lists_body<R>(a, c, rp.img, force, i - m * bpc, bpc);
+        build_lists_body<R>(rp.L, rp.c, rp.img, force, i - m * bpc, bpc);   // (the records stay where they are: a copy up front keeps every field live across the body)
         __syncthreads();   // (the next item reuses the body's LDS)
     }
 }

@@ -27,6 +27,10 @@ struct DevFlags {  // device-resident control words
     int prune_req;               // fragment lists (kernels_frag.h): an atom has moved half the inner margin since the last prune
 };
 
+// A list's kept superset (build_lists_body): every non-alchemical atom that lay within rsup of c0 when it was derived, and every
+// mobile non-alchemical atom wherever it is.  state: 0 none yet, 1 valid, -1 it would not fit (or holds more than half the atoms)
+struct SupHdr { unsigned long long c0[3]; float rsup; int state; int count; int pad; };
+
 struct ListArgs {
     int n, n_tiles, n_itiles, jcap, pool_cap;   // n_tiles: list blocks = n_lists (+1 with alchemical atoms)
     const int* tile_atoms;   // [n_tiles*64] sorted atom index or -1
@@ -44,8 +48,11 @@ struct ListArgs {
     // bookkeeping done by the same launch when a rebuild happens
     const double* x[3];      // master positions (caller order)
     double* xbuild[3];
-    double* fJ;              // [9*n] alchemical forces on environment atoms, zeroed on rebuild
-    int n_fJ;
+    double* fJ;              // [9*n] alchemical forces on environment atoms by sorted index; the MOBILE atoms' entries are zeroed on rebuild
+                             // (a frozen atom's entry is zero from the layout on -- every layout zero-fills the buffer -- and no kernel writes or reads it)
+    const int* mob_atoms;    // [n_mob] caller index of every atom that can move (mass != 0, alchemical atoms included): whose xbuild / fJ a rebuild touches
+    const int* sorted_of_orig;
+    int n_mob;
     // per-atom Verlet lists (nonbonded_atom_body): for every i-slot the LOCAL indices (positions in its tile's j-list) of
     // the atoms within cutoff+skin, exclusions already removed; bit 15 = that j is mobile (energy weight 1/2).  Null: not built.
     unsigned short* alist;   // [n_islots][acap]
@@ -69,6 +76,11 @@ struct ListArgs {
     unsigned short* aself;   // [n_islots] every i-atom's own entry in its group's list (NB_ENT form; 0xffff: not there), written with the atoms' lists
     uint4* pimgb;            // [n_lists][jcap] what the builder of the atoms' lists streams: {x, y, z, sorted atom index | mobile << 31}
     const int* sx_row;       // [n_islots][SX_ROW] static per i-slot: the atom's sorted index, its excluded partners, count / min / max (build_atom_lists_body)
+    // kept superset of a list's candidates (build_lists_body; null: the layout made no room for one, every rebuild scans all n atoms)
+    int* sup; SupHdr* sup_hdr; int sup_cap;   // [n_tiles][sup_cap] sorted indices, ascending; one header per list
+    float sup_slack;         // D (nm): how far the superset's sphere reaches beyond the list's own when it is derived; <= 0: switched off (every
+                             // rebuild scans all n atoms, and a rebuild the host forces still marks the headers "none yet")
+    int* sup_stat;           // [2] rebuilds in which list 0 was served from its superset / scanned every atom (counted while switched on)
     float pf_reach;          // prefilter of build_atom_lists_body: a wave whose atoms lie within this of their centre (nm) walks the prefiltered list; < 0: no wave does
 };
 
@@ -104,10 +116,18 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
     // ---- shared bookkeeping: remember where the lists were built, clear alchemical env forces
     if (t >= a.n_tiles) {  // helper blocks: bookkeeping that must not sit on a tile block's critical path
         const int hb = t - a.n_tiles, nh = nblocks - a.n_tiles;
-        for (int i = hb * LIST_THREADS + tid; i < a.n; i += nh * LIST_THREADS) {
-            a.xbuild[0][i] = a.x[0][i]; a.xbuild[1][i] = a.x[1][i]; a.xbuild[2][i] = a.x[2][i];
+        NB_STAMP(hb == 0 && tid == 0, 14);
+        // Only atoms that can move: xbuild is read for cluster atoms alone (step kernels, minimiser, constraints), and the alchemical
+        // kernels write -- and the step / finalize kernels read -- fJ for mobile entries alone.  (All n atoms and 9 n doubles used
+        // to pass through here: 2.8 MB per rebuilding chain of 23,400 atoms, 94 % of them frozen.)
+        for (int m = hb * LIST_THREADS + tid; m < a.n_mob; m += nh * LIST_THREADS) {
+            const int i = a.mob_atoms[m], js = a.sorted_of_orig[i];
+            const double x0 = a.x[0][i], x1 = a.x[1][i], x2 = a.x[2][i];
+            a.xbuild[0][i] = x0; a.xbuild[1][i] = x1; a.xbuild[2][i] = x2;
+#pragma unroll
+            for (int s = 0; s < 9; s++) a.fJ[(size_t)s * a.n + js] = 0.0;
         }
-        for (int i = hb * LIST_THREADS + tid; i < a.n_fJ; i += nh * LIST_THREADS) a.fJ[i] = 0.0;
+        NB_STAMP(hb == 0 && tid == 0, 15);
         return;
     }
 
@@ -124,6 +144,7 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
     const int tile0 = alch_tile ? a.n_itiles : t * a.S;
     const int ntile = alch_tile ? 1 : min(a.S, a.n_itiles - tile0);
     NB_STAMP(t == 0 && tid == 0, 0);
+    NB_STAMP(alch_tile && tid == 0, 11);
     if (alch_tile && wv == 1) {
         const int ia = a.tile_atoms[tile0 * 64 + lane];
         if (ia >= 0) { s_ax[lane][0] = img[ia].x; s_ax[lane][1] = img[ia].y; s_ax[lane][2] = img[ia].z; }
@@ -135,6 +156,9 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
     // i-slot (ntile <= 16); an atom can only be within range of some i-atom if it is within cutoff+skin of both
     __shared__ double s_lo[LIST_WAVES][3], s_hi[LIST_WAVES][3], s_r2[LIST_WAVES];
     __shared__ double s_mid[3], s_rad;
+    __shared__ int s_use, s_scount, s_state;
+    SupHdr H; H.state = 0; H.count = 0; H.rsup = 0.0f; H.c0[0] = H.c0[1] = H.c0[2] = 0ull;
+    if (a.sup && tid == 0) H = a.sup_hdr[t];   // (asked for here, wanted once the sphere is known)
     {
         const int i0 = a.tile_atoms[tile0 * 64];
         const ufix ref[3] = {img[i0].x, img[i0].y, img[i0].z};
@@ -166,7 +190,25 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
         for (int o = 32; o > 0; o >>= 1) r2 = fmax(r2, __shfl_xor(r2, o, 64));
         if (lane == 0) s_r2[wv] = r2;
         __syncthreads();
-        if (tid == 0) { double m = 0.0; for (int w = 0; w < LIST_WAVES; w++) m = fmax(m, s_r2[w]); s_rad = sqrt(m) + 4.0 * (c.dscale[0] + c.dscale[1] + c.dscale[2]); }
+        if (tid == 0) {
+            double m = 0.0; for (int w = 0; w < LIST_WAVES; w++) m = fmax(m, s_r2[w]);
+            const double rad = sqrt(m) + 4.0 * (c.dscale[0] + c.dscale[1] + c.dscale[2]);
+            s_rad = rad;
+            // ---- the kept superset serves this rebuild if the sphere a frozen candidate is tested against below (radius rsphf, squared
+            // with a factor 1.0001) lies inside the superset's: |centre - c0| + rsphf (1 + 1e-4) + 1e-4 nm <= rsup.  Differences of
+            // fixed-point coordinates are minimum images, which obey the triangle inequality; the float rounding of either distance
+            // is ~1e-6 nm.  Mobile atoms are in the superset wherever they are.  A rebuild the host forced (force == 1: positions
+            // replaced, a new layout or shape, a fault) trusts nothing kept and derives the superset again.
+            int use = 0;
+            if (a.sup && a.sup_slack > 0.0f && force != 1 && H.state == 1 && H.count > 0 && !a.no_sphere) {
+                float d2 = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 3; k++) { const float o = (float)(sfix)(s_cfix[k] - (ufix)H.c0[k]) * (float)c.dscale[k]; d2 = fmaf(o, o, d2); }
+                const float rsph = (float)rad * 1.00001f + 1e-6f + sqrtf((float)c.rlist2 * 1.0001f + 1e-5f);
+                use = sqrtf(d2) * 1.00001f + rsph * 1.0001f + 1e-4f <= H.rsup;
+            }
+            s_use = use; s_scount = H.count; s_state = H.state;
+        }
     }
     __syncthreads();
     const ufix cf[3] = {s_cfix[0], s_cfix[1], s_cfix[2]};
@@ -184,18 +226,36 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
     const float rl2f = (float)c.rlist2 * 1.0001f + 1e-5f, rl2m = (float)c.rlist2_m * 1.0001f + 1e-5f;   // frozen / mobile candidates
     const float rsphf = ((float)s_rad * 1.00001f + 1e-6f + sqrtf(rl2f)), rsphm = ((float)s_rad * 1.00001f + 1e-6f + sqrtf(rl2m));
     const float rs2f = a.no_sphere ? __builtin_inff() : rsphf * rsphf * 1.0001f, rs2m = a.no_sphere ? __builtin_inff() : rsphm * rsphm * 1.0001f;
-    const int j_end = min(a.n, (wv + 1) * share);
-    int wcount = 0;
-    for (int base = wv * share; base < j_end; base += 64 * LIST_PREFETCH) {
-        ufix px[LIST_PREFETCH], py[LIST_PREFETCH], pz[LIST_PREFETCH]; unsigned fl[LIST_PREFETCH];
+    // The candidates: all n atoms, or the list's kept superset (ascending sorted indices) where it still holds every atom the tests
+    // below can pass -- the same tests on the same atoms in the same order, so the same list entry for entry.  A scan of all atoms
+    // derives the superset beside the list, by a second ordered compaction (stage2, concatenated like the list).
+    const bool use_sup = s_use != 0;
+    const bool make_sup = a.sup && a.sup_slack > 0.0f && !use_sup && !a.no_sphere && (force == 1 || s_state != -1);
+    int* supl = a.sup + (size_t)t * a.sup_cap;
+    int* stage2 = a.jstage + ((size_t)(a.n_tiles + t) * LIST_WAVES + wv) * share;
+    const float rsup = rsphf * 1.0001f + a.sup_slack, rsup2 = rsup * rsup;
+    const int scount = use_sup ? s_scount : a.n;
+    const int sshare = use_sup ? ((((scount + LIST_WAVES - 1) / LIST_WAVES) + 63) & ~63) : share;   // (<= share: a superset holds at most n / 2)
+    const int j_end = min(scount, (wv + 1) * sshare);
+    int wcount = 0, wcount2 = 0;
+    int jn[LIST_PREFETCH];
+#pragma unroll
+    for (int u = 0; u < LIST_PREFETCH; u++) jn[u] = use_sup ? supl[min(wv * sshare + u * 64 + lane, scount - 1)] : 0;
+    for (int base = wv * sshare; base < j_end; base += 64 * LIST_PREFETCH) {
+        ufix px[LIST_PREFETCH], py[LIST_PREFETCH], pz[LIST_PREFETCH]; unsigned fl[LIST_PREFETCH]; int jj[LIST_PREFETCH];
 #pragma unroll
         for (int u = 0; u < LIST_PREFETCH; u++) {   // all loads of the group are issued before the first is consumed
-            const int j = min(base + u * 64 + lane, a.n - 1);
+            const int j = use_sup ? jn[u] : min(base + u * 64 + lane, a.n - 1);
+            jj[u] = j;
             px[u] = img[j].x; py[u] = img[j].y; pz[u] = img[j].z; fl[u] = img[j].flags;
+        }
+        if (use_sup) {   // the next group's indices travel beside this group's atoms
+#pragma unroll
+            for (int u = 0; u < LIST_PREFETCH; u++) jn[u] = supl[min(base + (LIST_PREFETCH + u) * 64 + lane, scount - 1)];
         }
 #pragma unroll
         for (int u = 0; u < LIST_PREFETCH; u++) {
-            const int j = base + u * 64 + lane;
+            const int idx = base + u * 64 + lane, j = jj[u];
             const ufix pj[3] = {px[u], py[u], pz[u]};
             float d2 = 0.0f, o2 = 0.0f;
 #pragma unroll
@@ -208,7 +268,13 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
             }
             const bool mob = (fl[u] & FLAG_MOBILE) != 0;
             const float rl2 = mob ? rl2m : rl2f, rs2 = mob ? rs2m : rs2f;
-            bool pass = j < j_end && d2 < rl2 && o2 < rs2 && !(fl[u] & FLAG_ALCH);
+            bool pass = idx < j_end && d2 < rl2 && o2 < rs2 && !(fl[u] & FLAG_ALCH);
+            if (make_sup) {
+                const bool keep = idx < j_end && !(fl[u] & FLAG_ALCH) && (mob || o2 < rsup2);
+                const unsigned long long bal2 = __ballot(keep);
+                if (keep) stage2[wcount2 + __popcll(bal2 & ((1ull << lane) - 1ull))] = j;
+                wcount2 += __popcll(bal2);
+            }
             if (alch_tile && pass) {
                 // the alchemical kernel spends a thread on every (j, alchemical atom) pair of this list, so the list is
                 // made exact: j stays only if it is within cutoff+skin of at least one alchemical atom (the bounding
@@ -227,8 +293,10 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
             wcount += __popcll(bal);
         }
     }
-    if (lane == 0) s_wcount[wv] = wcount;
+    __shared__ int s_wcount2[LIST_WAVES];
+    if (lane == 0) { s_wcount[wv] = wcount; s_wcount2[wv] = wcount2; }
     NB_STAMP(t == 0 && tid == 0, 2);
+    NB_STAMP(alch_tile && tid == 0, 12);
     __syncthreads();
     NB_STAMP(t == 0 && tid == 0, 3);
     {
@@ -237,10 +305,20 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
         for (int k = lane; k < wcount; k += 64) if (off + k < a.jcap) jl[off + k] = stage[k];
         if (tid == 0) { int tot = 0; for (int w = 0; w < LIST_WAVES; w++) tot += s_wcount[w]; s_total = tot; }
     }
+    if (make_sup) {
+        int off2 = 0, tot2 = 0;
+        for (int w = 0; w < LIST_WAVES; w++) { if (w < wv) off2 += s_wcount2[w]; tot2 += s_wcount2[w]; }
+        const bool fits = tot2 > 0 && tot2 <= a.sup_cap && 2 * tot2 <= a.n;   // (all-mobile systems, tiny boxes: never valid, the scan of all atoms for good)
+        if (fits) for (int k = lane; k < wcount2; k += 64) supl[off2 + k] = stage2[k];
+        if (tid == 0) {
+            SupHdr N; N.c0[0] = cf[0]; N.c0[1] = cf[1]; N.c0[2] = cf[2]; N.rsup = rsup; N.state = fits ? 1 : -1; N.count = fits ? tot2 : 0; N.pad = 0;
+            a.sup_hdr[t] = N;
+        }
+    } else if (a.sup && force == 1 && tid == 0) a.sup_hdr[t].state = 0;   // (switched off, or no sphere test: what is kept predates what the host changed)
     __threadfence_block();
     __syncthreads();
     int count = s_total;
-    if (t == 0 && tid == 0) a.flags->builds++;
+    if (t == 0 && tid == 0) { a.flags->builds++; if (a.sup && a.sup_slack > 0.0f) a.sup_stat[use_sup ? 0 : 1]++; }
     const int cap_eff = (!alch_tile && a.alist && a.pimg4) ? a.jcap - 1 : a.jcap;   // (per-atom-list mode: the image keeps one entry for the ghost)
     if (count > cap_eff) { if (tid == 0) a.flags->list_overflow = 1; count = cap_eff; }
     else if (count > a.hint_count && tid == 0) a.flags->resort_hint = 1;
@@ -258,6 +336,7 @@ __device__ __forceinline__ void build_lists_body(const ListArgs& a, const NbCons
             r.sig = a.p_sigma[jo]; r.eps = sqrt(a.p_eps[jo]); r.q = a.p_charge[jo];   // (eps: its square root, see AlchJRec)
             jr[k] = r;
         }
+        NB_STAMP(tid == 0, 13);
         return;
     }
 

@@ -57,6 +57,10 @@ class NativeEngine:
         spec = os.environ.get("BLUES_ATOM_LIST_PREFILTER")
         if spec:
             self._check(self._lib.blues_set_global(self._h, b"atom_list_prefilter", float(int(spec))))
+        # development switch of the group lists' kept supersets: 0 = every rebuild scans all atoms, N = slack of N picometres
+        spec = os.environ.get("BLUES_GROUP_LIST_SUPERSET")
+        if spec:
+            self._check(self._lib.blues_set_global(self._h, b"group_list_superset", float(int(spec))))
         if system.positions is not None:
             self.set_positions(system.positions)
 
