@@ -79,7 +79,13 @@ class BluesImplicitSolventDesc(C.Structure):
 
 class BluesSystemExt(C.Structure):
     """include/blues_engine.h: BluesSystemExt (additive System options; blues_engine_create_ext)."""
-    _fields_ = [("struct_size", C.c_int32), ("alchemical_pme_treatment", C.c_int32)]
+    _fields_ = [("struct_size", C.c_int32), ("alchemical_pme_treatment", C.c_int32),
+                ("n_cmap_maps", C.c_int32), ("cmap_size", _ip), ("cmap_energy", _dp),
+                ("n_cmap_torsions", C.c_int32), ("cmap_torsion_map", _ip), ("cmap_torsion_atoms", _ip)]
+
+
+SYSTEM_EXT_SIZE_V1 = 8                     # a caller from before the CMAP fields: struct_size, alchemical_pme_treatment
+CMAP_MIN_SIZE, CMAP_MAX_SIZE = 4, 64       # BLUES_CMAP_MIN_SIZE / BLUES_CMAP_MAX_SIZE
 
 
 # SystemData.alchemical_pme_treatment -> BluesSystemExt.alchemical_pme_treatment (BLUES_ALCH_PME_*)
@@ -117,7 +123,7 @@ class BluesMinimizeResult(C.Structure):
 MINIMIZE_FIELDS = ("dt0", "dt_max", "f_inc", "f_dec", "alpha0", "f_alpha", "max_step", "n_min")
 # additive entry points (BLUES_ABI_VERSION unchanged): a library built before them loads, and the wrappers that need them say so
 MINIMIZE_SYMBOLS = ("blues_minimize_default", "blues_minimize", "blues_batch_minimize")
-OPTIONAL_SYMBOLS = MINIMIZE_SYMBOLS + ("blues_engine_create_ext", "blues_get_exact_pme_path")
+OPTIONAL_SYMBOLS = MINIMIZE_SYMBOLS + ("blues_engine_create_ext", "blues_get_exact_pme_path", "blues_get_cmap_angles")
 
 
 class BluesTuning(C.Structure):
@@ -219,6 +225,8 @@ class SystemData:
     centroid_bonds: tuple = ()           # NB_NOCUTOFF only; entries (idx1, w1, idx2, w2, k): E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w)
     implicit_solvent: ImplicitSolventData = None   # NB_NOCUTOFF only; GB-OBC with the ACE surface term (blues_engine_create_gb)
     alchemical_pme_treatment: str = "direct-space"   # NB_PME: "direct-space" or "exact" (openmmtools' alchemical_pme_treatment; blues_engine_create_ext)
+    cmap_maps: tuple = ()                # CMAPTorsionForce maps: (n, n) arrays, kJ/mol, E[i, j] at phi = 2 pi i / n, psi = 2 pi j / n (blues_engine_create_ext)
+    cmap_torsions: np.ndarray = field(default_factory=lambda: np.zeros((0, 9), np.int32))   # (m, 9): map, a1..a4 (phi), b1..b4 (psi)
 
     def __post_init__(self):
         alchemical_pme_treatment_code(self.alchemical_pme_treatment)
@@ -245,14 +253,51 @@ class SystemData:
             raise ValueError("alchemical_pme_treatment 'exact' with a switching_mode integrator is not supported: its force and energy "
                              "bookkeeping does not know the exact treatment's terms")
 
+    @property
+    def has_cmap(self):
+        return len(tuple(self.cmap_maps or ())) > 0 or np.asarray(self.cmap_torsions).size > 0
+
     def ext_desc(self):
-        """BluesSystemExt of this System, or None where blues_engine_create / blues_engine_create_gb say everything."""
+        """BluesSystemExt of this System, or None where blues_engine_create / blues_engine_create_gb say everything.  The numpy
+        buffers of the maps stay alive with the descriptor (its _keep)."""
         code = alchemical_pme_treatment_code(self.alchemical_pme_treatment)
-        if code == 0:
+        if code == 0 and not self.has_cmap:
             return None
         d = BluesSystemExt()
         d.struct_size = C.sizeof(BluesSystemExt); d.alchemical_pme_treatment = code
+        if self.has_cmap:
+            maps = [_f64(m) for m in self.cmap_maps]
+            tors = _i32(self.cmap_torsions, (-1, 9))
+            keep = {"size": _i32([m.shape[0] for m in maps], (-1,)),
+                    # E[i, j] is stored energy[i + n * j]: the transpose, row by row
+                    "energy": _f64(np.concatenate([m.T.reshape(-1) for m in maps]) if maps else np.zeros(0), (-1,)),
+                    "map": _i32(tors[:, 0], (-1,)), "atoms": _i32(tors[:, 1:], (-1,))}
+            d.n_cmap_maps = len(maps); d.n_cmap_torsions = len(tors)
+            d.cmap_size = keep["size"].ctypes.data_as(_ip); d.cmap_energy = keep["energy"].ctypes.data_as(_dp)
+            d.cmap_torsion_map = keep["map"].ctypes.data_as(_ip); d.cmap_torsion_atoms = keep["atoms"].ctypes.data_as(_ip)
+            d._keep = keep
         return d
+
+    def check_cmap(self):
+        """What blues_engine_create_ext refuses about the CMAP maps and torsions, raised before a library is loaded (ValueError)."""
+        maps = tuple(self.cmap_maps or ())
+        tors = np.asarray(self.cmap_torsions)
+        if tors.size and (tors.ndim != 2 or tors.shape[1] != 9):
+            raise ValueError("cmap_torsions: an (m, 9) array of map, a1..a4, b1..b4; got shape %s" % (tors.shape,))
+        for k, m in enumerate(maps):
+            m = np.asarray(m, dtype=np.float64)
+            if m.ndim != 2 or m.shape[0] != m.shape[1] or not CMAP_MIN_SIZE <= m.shape[0] <= CMAP_MAX_SIZE:
+                raise ValueError("CMAP map %d: size %s; a map is n x n with n from %d to %d" % (k, "x".join(str(q) for q in m.shape), CMAP_MIN_SIZE, CMAP_MAX_SIZE))
+            if not np.all(np.isfinite(m)):
+                raise ValueError("CMAP map %d: an energy is not finite" % k)
+        for t, row in enumerate(tors.reshape(-1, 9)):
+            if row[0] < 0 or row[0] >= len(maps):
+                raise ValueError("CMAP torsion %d: map %d of %d" % (t, row[0], len(maps)))
+            if np.any(row[1:] < 0) or np.any(row[1:] >= self.n_atoms):
+                raise ValueError("CMAP torsion %d: atom index out of range" % t)
+            for d in (row[1:5], row[5:9]):
+                if len(set(int(a) for a in d)) != 4:
+                    raise ValueError("CMAP torsion %d: two equal atoms within one dihedral" % t)
 
     def check_custom_forces(self):
         """What blues_engine_create refuses about the two custom forces, raised before a library is loaded (ValueError)."""
@@ -454,6 +499,7 @@ def declare_engine_prototypes(lib):
         "blues_reset": ([H], C.c_int),
         "blues_get_stats": ([H, C.POINTER(C.c_int64)], C.c_int),
         "blues_get_exact_pme_path": ([H, C.POINTER(C.c_int64)], C.c_int),
+        "blues_get_cmap_angles": ([H, _dp], C.c_int),
         "blues_time_nonbonded": ([H, C.c_int32, _dp], C.c_int),
         "blues_time_list_build": ([H, C.c_int32, _dp], C.c_int),
         "blues_audit_lists": ([H, C.POINTER(C.c_int64)], C.c_int),
@@ -505,7 +551,7 @@ ENGINE_SYMBOLS = (
     "blues_set_positions", "blues_set_velocities", "blues_set_box", "blues_get_positions",
     "blues_get_velocities", "blues_get_forces", "blues_get_box", "blues_set_velocities_to_temperature",
     "blues_get_energy", "blues_get_energy_at", "blues_get_energy_terms", "blues_mesh_energy", "blues_step", "blues_run_switch", "blues_get_global",
-    "blues_set_global", "blues_reset", "blues_get_stats", "blues_get_exact_pme_path", "blues_time_nonbonded", "blues_time_list_build", "blues_audit_lists",
+    "blues_set_global", "blues_reset", "blues_get_stats", "blues_get_exact_pme_path", "blues_get_cmap_angles", "blues_time_nonbonded", "blues_time_list_build", "blues_audit_lists",
     "blues_snapshot_capture", "blues_snapshot_release", "blues_snapshot_read", "blues_set_positions_from_snapshot",
     "blues_set_velocities_from_snapshot", "blues_snapshot_read_atoms", "blues_set_positions_from_snapshot_edited",
     "blues_batch_create", "blues_batch_destroy", "blues_batch_last_error", "blues_batch_size", "blues_batch_step", "blues_batch_set_active", "blues_batch_prefetch_energies",

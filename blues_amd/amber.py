@@ -125,6 +125,56 @@ def ewald_alpha(cutoff, tolerance):
     return float(np.sqrt(-np.log(2.0 * tolerance)) / cutoff)
 
 
+def cmap_from_prmtop(prm, natom=None):
+    """The CMAP sections of a prmtop -> (maps, torsions) as SystemData.cmap_maps / .cmap_torsions hold them; ((), empty) without them.
+
+    Sections CMAP_COUNT, CMAP_RESOLUTION, CMAP_PARAMETER_NN, CMAP_INDEX (Amber ff19SB) or the same names prefixed CHARMM_ (chamber).
+    The layout is recalled from ParmEd, not source-pinned: CMAP_COUNT = (terms, types); CMAP_INDEX holds six integers
+    per term, five 1-based atom numbers and a 1-based type; a parameter section holds res^2 values in kcal/mol, phi the slow index,
+    both angles starting at -180 degrees.  OpenMM's maps start at 0: E[i, j] = 4.184 G[(i + res/2) mod res][(j + res/2) mod res].
+    The five atoms a1..a5 become the torsion (a1, a2, a3, a4, a2, a3, a4, a5).  ValueError, with the reason, for an odd resolution,
+    counts that do not match the sections and a type or atom out of range."""
+    empty = ((), np.zeros((0, 9), np.int32))
+    prefix = None
+    for cand in ("", "CHARMM_"):
+        if cand + "CMAP_COUNT" in prm:
+            prefix = cand
+            break
+    if prefix is None:
+        return empty
+    count = np.asarray(prm[prefix + "CMAP_COUNT"]).reshape(-1)
+    if len(count) != 2:
+        raise ValueError("%sCMAP_COUNT holds %d values, not (terms, types)" % (prefix, len(count)))
+    nterm, ntype = int(count[0]), int(count[1])
+    res = np.asarray(prm.get(prefix + "CMAP_RESOLUTION", ())).reshape(-1)
+    if len(res) != ntype:
+        raise ValueError("%sCMAP_COUNT names %d types but %sCMAP_RESOLUTION holds %d" % (prefix, ntype, prefix, len(res)))
+    maps = []
+    for k in range(ntype):
+        n = int(res[k])
+        if n % 2:
+            raise ValueError("CMAP type %d: odd resolution %d (a map that starts at -180 degrees cannot be shifted to start at 0)" % (k + 1, n))
+        name = "%sCMAP_PARAMETER_%02d" % (prefix, k + 1)
+        g = np.asarray(prm.get(name, ()), dtype=np.float64).reshape(-1)
+        if len(g) != n * n:
+            raise ValueError("%s holds %d values, resolution %d needs %d" % (name, len(g), n, n * n))
+        shift = (np.arange(n) + n // 2) % n
+        maps.append(KCAL * g.reshape(n, n)[np.ix_(shift, shift)])
+    index = np.asarray(prm.get(prefix + "CMAP_INDEX", ()), dtype=np.int64).reshape(-1)
+    if len(index) != 6 * nterm:
+        raise ValueError("%sCMAP_COUNT names %d terms but %sCMAP_INDEX holds %d integers (six per term)" % (prefix, nterm, prefix, len(index)))
+    index = index.reshape(-1, 6)
+    tors = np.zeros((nterm, 9), np.int32)
+    for t, row in enumerate(index):
+        if row[5] < 1 or row[5] > ntype:
+            raise ValueError("CMAP term %d: type %d of %d" % (t + 1, row[5], ntype))
+        a = row[:5] - 1
+        if np.any(a < 0) or (natom is not None and np.any(a >= natom)):
+            raise ValueError("CMAP term %d: atom out of range" % (t + 1))
+        tors[t] = (row[5] - 1, a[0], a[1], a[2], a[3], a[1], a[2], a[3], a[4])
+    return tuple(maps), tors
+
+
 def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.005, constraints="HBonds",
                       rigid_water=True, hydrogen_mass=None, remove_cm_motion=True, alchemical_atoms=(),
                       tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME",
@@ -331,6 +381,8 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
         residue_of_atom=residue_of_atom, names=list(prm.get("ATOM_NAME", [])),
         implicit_solvent=gb, alchemical_pme_treatment=alchemical_pme_treatment,
     )
+    system.cmap_maps, system.cmap_torsions = cmap_from_prmtop(prm, natom)   # (CMAPTorsionForce of ff19SB / chamber topologies)
+    system.check_cmap()
     system.check_implicit_solvent()
     system.check_alchemical_pme_treatment()
     return system

@@ -44,6 +44,7 @@
 #include "kernels_minimize.h"
 static_assert(CENT_GROUP == BLUES_MAX_CENTROID_GROUP, "a centroid-bond term has one place per atom the C-ABI allows in a group (kernels_bonded.h, build_bonded)");
 static_assert(T_CENT >= T_NTYPES, "T_CENT is an entry type only: it has no slot in the per-type arrays");
+static_assert(T_CMAP > T_CENT, "T_CMAP is an entry type only, past T_CENT");
 
 static thread_local std::string g_create_error;
 // set-up cost accounting (diagnostic, blues_debug_setup_seconds): [0] blues_engine_create, [1] sort_and_tile, [2] its device uploads,
@@ -206,6 +207,11 @@ struct HostTopology {
     std::vector<std::vector<int>> excl;          // per atom, both directions
     std::vector<int> alch_local;                 // [n] -> local alchemical index or -1
     std::vector<int32_t> link_pairs;             // bonds and constraints: what holds a molecule together
+    // CMAP torsion maps (BluesSystemExt): sizes, energies and torsions as the caller gave them; first patch of every map and the 16
+    // polynomial coefficients of every patch (cmap_tables), and the device copy of those per device, shared by the System's engines
+    std::vector<int32_t> cmap_size, cmap_tor_map, cmap_tor_atoms, cmap_first;
+    std::vector<double> cmap_energy, cmap_coef;
+    std::mutex cmap_mu; std::map<int, std::shared_ptr<DBuf<double>>> cmap_dev;
 };
 
 struct BluesEngine {
@@ -376,6 +382,7 @@ struct BluesEngine {
     DBuf<int> d_term_atoms[T_NTYPES]; DBuf<double> d_term_params[T_NTYPES];
     int n_terms[T_NTYPES] = {0, 0, 0, 0, 0, 0}; int n_rows = 0; double restr_k = 0;
     int n_cent = 0; DBuf<int> d_cent_atoms; DBuf<double> d_cent_params;   // harmonic centroid bonds (kernels_bonded.h: T_CENT, the CENT = true kernels)
+    int n_cmap = 0; DBuf<int> d_cmap_atoms, d_cmap_grid; std::shared_ptr<DBuf<double>> d_cmap_coef; DBuf<double> d_cmap_angles;   // CMAP torsions (T_CMAP, the CMAP = true kernels)
     // pending integrate program
     Program prog; unsigned prog_draw_base = 0; int prog_trace = -1; bool tracing = false;
     // stats
@@ -889,6 +896,28 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
         }
         h->d_cent_atoms.upload(at); h->d_cent_params.upload(w);
     }
+    // CMAP torsions (validated by create_impl): every mobile atom of a torsion owns ONE entry (type T_CMAP, role = the first of the eight
+    // places that names it; the kernel adds the part of every place that does, in place order); all atoms frozen: energy only
+    h->n_cmap = (int)h->T->cmap_tor_map.size();
+    if (h->n_cmap > 0) {
+        std::vector<int> grid((size_t)2 * h->n_cmap);
+        for (int t = 0; t < h->n_cmap; t++) {
+            const int mp = h->T->cmap_tor_map[t];
+            grid[2 * t] = h->T->cmap_size[mp]; grid[2 * t + 1] = h->T->cmap_first[mp];
+            const int32_t* q = h->T->cmap_tor_atoms.data() + 8 * (size_t)t;
+            for (int pl = 0; pl < 8; pl++) {
+                bool first = true;
+                for (int o = 0; o < pl; o++) if (q[o] == q[pl]) first = false;
+                if (first && h->T->mass[q[pl]] != 0.0) { rtype[q[pl]].push_back(T_CMAP); rterm[q[pl]].push_back(t); rrole[q[pl]].push_back(pl); }
+            }
+        }
+        h->d_cmap_atoms.upload(std::vector<int>(h->T->cmap_tor_atoms.begin(), h->T->cmap_tor_atoms.end())); h->d_cmap_grid.upload(grid);
+        h->d_cmap_angles.alloc((size_t)2 * h->n_cmap);
+        std::lock_guard<std::mutex> lk(h->T->cmap_mu);
+        std::shared_ptr<DBuf<double>>& dev = h->T->cmap_dev[h->device];
+        if (!dev) { dev = std::make_shared<DBuf<double>>(); dev->upload(h->T->cmap_coef); }
+        h->d_cmap_coef = dev;
+    }
     std::vector<int> row_atom, row_start(1, 0), et, ei, er;
     for (int i = 0; i < h->n; i++) if (!rtype[i].empty()) {
         row_atom.push_back(i);
@@ -899,7 +928,7 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
     { std::vector<int> row_of(h->n, -1); for (int r = 0; r < h->n_rows; r++) row_of[row_atom[r]] = r; h->d_row_of_orig.upload(row_of); h->h_row_of_orig = row_of; h->h_row_start = row_start; }
     h->d_fent.alloc((size_t)3 * std::max(1, h->n_entries));
     h->d_row_atom.upload(row_atom); h->d_row_start.upload(row_start); h->d_ent_type.upload(et); h->d_ent_term.upload(ei); h->d_ent_role.upload(er);
-    int total_terms = h->n_cent; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
+    int total_terms = h->n_cent + h->n_cmap; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     h->d_epart_b.alloc((size_t)((total_terms + 255) / 256 + 1) * T_NTYPES);
     // alchemical exception rows
     std::vector<int> es(1, 0), ep, eo; std::vector<double> epar;
@@ -1116,6 +1145,7 @@ static int sort_and_tile(BluesEngine* h) {
         h->fuse_forces = nit * h->batch_R <= 32;
         if (h->tune.fuse_forces >= 0) h->fuse_forces = h->tune.fuse_forces != 0;
         if (h->n_gen()) h->fuse_forces = false;   // (general constraint clusters: the decomposed force pass and k_finalize only)
+        if (h->n_cmap > 0) h->fuse_forces = false;   // (CMAP torsions: the fused force launch runs the plain bonded body, which does not know the entry type)
         if (h->fuse_forces) { WPB = 4; NW = std::max(4, NW / 3); }  // ~3 segments per wave: as long as the alchemical role
         NW = std::max(WPB, (NW / WPB) * WPB);
         if (h->pin_jcap > 0 && h->batch && std::min<double>(n, est / 1.8 * 1.2) + 64 <= h->pin_jcap) { jcap = h->pin_jcap; h->jcap = jcap; CH = h->pin_seg; NW = h->pin_nw; WPB = h->pin_wpb; }
@@ -1935,6 +1965,7 @@ static BondedArgs make_bonded_args(BluesEngine* h) {
     B.box = make_box(h); B.periodic = h->nb_method == BLUES_NB_PME_DIRECT; B.fent = h->d_fent.p; B.n_entries = h->n_entries; B.n = h->n; B.epart = h->d_epart_b.p;
     B.n_mobile = (int)h->mobile.size(); B.n_noise = h->n_noise; B.mobile_atoms = h->d_mobile_atoms.p; B.noise = h->d_noise.p;
     B.n_cent = h->n_cent; B.cent_atoms = h->d_cent_atoms.p; B.cent_params = h->d_cent_params.p;
+    B.n_cmap = h->n_cmap; B.cmap_atoms = h->d_cmap_atoms.p; B.cmap_grid = h->d_cmap_grid.p; B.cmap_coef = h->d_cmap_coef ? h->d_cmap_coef->p : nullptr;
     B.seed = h->seed; B.stream = (unsigned)h->replica * 4u; B.draw_base = h->h_draw; B.n_entry_blocks = (h->n_entries + 127) / 128;
     return B;
 }
@@ -1945,7 +1976,11 @@ static int launch_bonded(BluesEngine* h, bool with_noise) {
     if (with_noise) { h->noise_draw_base = h->h_draw; h->noise_valid = true; }
     if (B.n_entry_blocks + nb_noise > 0) {
         BondedDyn D; D.draw_base = B.draw_base; D.n_entry_blocks = B.n_entry_blocks;
-        if (h->n_cent > 0) {   // (centroid bonds: the instantiations that know the entry type)
+        if (h->n_cmap > 0) {   // (CMAP torsions: the instantiations that know both entry-only types)
+            if (batch_lead(h)) hipLaunchKernelGGL((k_bonded_entries_b<true, true>), dim3(B.n_entry_blocks + nb_noise, h->batch->R()), dim3(128), 0, h->cur, h->batch->d_core.p, D);
+            else if (!batch_dry(h)) hipLaunchKernelGGL((k_bonded_entries<true, true>), dim3(B.n_entry_blocks + nb_noise), dim3(128), 0, h->cur, B);
+        }
+        else if (h->n_cent > 0) {   // (centroid bonds: the instantiations that know the entry type)
             if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_entries_b<true>, dim3(B.n_entry_blocks + nb_noise, h->batch->R()), dim3(128), 0, h->cur, h->batch->d_core.p, D);
             else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_entries<true>, dim3(B.n_entry_blocks + nb_noise), dim3(128), 0, h->cur, B);
         }
@@ -2359,6 +2394,8 @@ static int force_pass(BluesEngine* h, int base_L) {
     if ((h->n_cent > 0 || h->pair_mode != BLUES_PAIR_STANDARD) && (h->k1_mode != 4 || h->fuse_forces || h->k2_dense))
         E_FAIL(h, "internal: an engine with custom forces left the decomposed NoCutoff path (k1_mode %d, fuse_forces %d, k2_dense %d)", h->k1_mode, (int)h->fuse_forces, (int)h->k2_dense);
 
+    if (h->n_cmap > 0 && h->fuse_forces)
+        E_FAIL(h, "internal: an engine with CMAP torsions was laid out for the fused force launch, whose bonded body does not know them");
     if (h->n_gen() && (h->fast_step || h->fuse_forces || fin_fusable(h)))
         E_FAIL(h, "internal: an engine with general constraint clusters was laid out for a fused kernel (fast_step %d, fuse_forces %d)", (int)h->fast_step, (int)h->fuse_forces);
 
@@ -2566,7 +2603,7 @@ static EnergyShape energy_shape(const BluesEngine* h) {
     if (h->k1_mode == 3) { g.nw = h->frag_nwg; g.off_frozen = (size_t)2 * h->frag_nwg; }   // one (LJ, Coulomb) pair per workgroup of the fragment kernel
     if (h->k1_mode == 4) { g.nw = h->nc_blocks_e; g.off_frozen = (size_t)2 * h->nc_blocks_e; }   // one (LJ, Coulomb) pair per block of the all-pairs kernel (it has every pair: no frozen-frozen constant)
     if (h->pair_mode == BLUES_PAIR_ETHYLENE) g.nw = 0;   // (the all-pairs kernel is not launched: launch_nocut)
-    int total_terms = h->n_cent; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
+    int total_terms = h->n_cent + h->n_cmap; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     g.nbb = (total_terms + 255) / 256; g.nfb = (h->n + FROZEN_TILE - 1) / FROZEN_TILE;
     return g;
 }
@@ -2593,7 +2630,11 @@ static int energy_launch(BluesEngine* h) {
     if (launch_pme_exact(h, le)) return 1;
     const EnergyShape g = energy_shape(h);
     if (g.nbb > 0) {
-        pick_tag<std::true_type, std::false_type>(h->n_cent > 0, [&](auto cent) {   // (with / without centroid bonds)
+        if (h->n_cmap > 0) {   // (CMAP torsions: the instantiations that know both entry-only types)
+            if (batch_lead(h)) hipLaunchKernelGGL((k_bonded_energy_b<true, true>), dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
+            else if (!batch_dry(h)) hipLaunchKernelGGL((k_bonded_energy<true, true>), dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
+        }
+        else pick_tag<std::true_type, std::false_type>(h->n_cent > 0, [&](auto cent) {   // (with / without centroid bonds)
             constexpr bool CENT = decltype(cent)::value;
             if (batch_lead(h)) hipLaunchKernelGGL(k_bonded_energy_b<CENT>, dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
             else if (!batch_dry(h)) hipLaunchKernelGGL(k_bonded_energy<CENT>, dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
@@ -3025,6 +3066,7 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
     if (nocut(a) != nocut(b)) { *why = "nonbonded method (a NoCutoff engine and a periodic one cannot share a batch)"; return false; }
     if (a->led_flags != b->led_flags) { *why = "measure_shadow_work / measure_heat (measuring and non-measuring members cannot share a batch)"; return false; }
     if (a->pair_mode != b->pair_mode || a->n_cent != b->n_cent) { *why = "custom forces (members with and without the custom pair form or centroid bonds cannot share a batch)"; return false; }
+    if (a->n_cmap != b->n_cmap || (a->n_cmap > 0 && a->T != b->T && (a->T->cmap_size != b->T->cmap_size || a->T->cmap_energy != b->T->cmap_energy || a->T->cmap_tor_map != b->T->cmap_tor_map || a->T->cmap_tor_atoms != b->T->cmap_tor_atoms))) { *why = "CMAP torsions (the members' maps or torsions differ)"; return false; }
     if (a->pme_exact != b->pme_exact) { *why = "alchemical_pme_treatment (members with the exact and the direct-space treatment cannot share a batch)"; return false; }
     if ((a->gb_model != 0) != (b->gb_model != 0)) { *why = "implicit solvent (members with and without it cannot share a batch)"; return false; }
     if (a->gb_model != b->gb_model || a->gb_eps_in != b->gb_eps_in || a->gb_eps_out != b->gb_eps_out || a->gb_sa_energy != b->gb_sa_energy || a->gb_radius != b->gb_radius || a->gb_scale != b->gb_scale) { *why = "implicit solvent (model, dielectrics, surface term, radii or scales differ)"; return false; }
@@ -3508,9 +3550,69 @@ static int build_pmex_pairs(BluesEngine* h, const BluesSystemDesc* s) {
     return 0;
 }
 
+// CMAP (include/blues_engine.h): knot derivatives of the periodic C2 cubic spline through y[0..n) at spacing 1 -- the cyclic system
+// d[k-1] + 4 d[k] + d[k+1] = 3 (y[k+1] - y[k-1]), solved densely (n <= 64, diagonally dominant: no pivoting), every column of `rhs` at once
+static void cmap_spline_derivatives(int n, std::vector<double>& rhs /* [n][n]: row k = knot, column = which curve; in: y, out: d */) {
+    std::vector<double> A((size_t)n * n, 0.0), b((size_t)n * n);
+    for (int k = 0; k < n; k++) {
+        A[(size_t)k * n + k] = 4.0; A[(size_t)k * n + (k + 1) % n] += 1.0; A[(size_t)k * n + (k + n - 1) % n] += 1.0;
+        for (int c = 0; c < n; c++) b[(size_t)k * n + c] = 3.0 * (rhs[(size_t)((k + 1) % n) * n + c] - rhs[(size_t)((k + n - 1) % n) * n + c]);
+    }
+    for (int k = 0; k < n; k++)
+        for (int r = k + 1; r < n; r++) {
+            const double f = A[(size_t)r * n + k] / A[(size_t)k * n + k];
+            if (f == 0.0) continue;
+            for (int c = k; c < n; c++) A[(size_t)r * n + c] -= f * A[(size_t)k * n + c];
+            for (int c = 0; c < n; c++) b[(size_t)r * n + c] -= f * b[(size_t)k * n + c];
+        }
+    for (int k = n - 1; k >= 0; k--)
+        for (int c = 0; c < n; c++) {
+            double v = b[(size_t)k * n + c];
+            for (int q = k + 1; q < n; q++) v -= A[(size_t)k * n + q] * rhs[(size_t)q * n + c];
+            rhs[(size_t)k * n + c] = v / A[(size_t)k * n + k];
+        }
+}
+// ... and from them the 16 coefficients c[a][b] of every bicubic Hermite patch in its local coordinates t, u in [0, 1] (derivatives per
+// grid step: the kernel multiplies dE/dt by n / 2 pi), patch (i, j) at 16 (first + i + n j)
+static void cmap_tables(HostTopology& T) {
+    static const double M[4][4] = {{1, 0, 0, 0}, {0, 0, 1, 0}, {-3, 3, -2, -1}, {2, -2, 1, 1}};   // (f0, f1, f'0, f'1) -> coefficients of 1, t, t^2, t^3
+    size_t first = 0, at = 0;
+    for (size_t mp = 0; mp < T.cmap_size.size(); mp++) {
+        const int n = T.cmap_size[mp];
+        const double* E = T.cmap_energy.data() + at;   // E[i + n j]
+        auto idx = [n](int i, int j) { return (size_t)((i + n) % n) + (size_t)n * ((j + n) % n); };
+        std::vector<double> w((size_t)n * n), d1((size_t)n * n), d2((size_t)n * n), d12((size_t)n * n);
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) w[(size_t)i * n + j] = E[idx(i, j)];   // knots along i, one curve per j
+        cmap_spline_derivatives(n, w);
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) d1[idx(i, j)] = w[(size_t)i * n + j];
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) w[(size_t)j * n + i] = E[idx(i, j)];   // knots along j, one curve per i
+        cmap_spline_derivatives(n, w);
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) d2[idx(i, j)] = w[(size_t)j * n + i];
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) w[(size_t)j * n + i] = d1[idx(i, j)];   // the spline through d1 along j
+        cmap_spline_derivatives(n, w);
+        for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) d12[idx(i, j)] = w[(size_t)j * n + i];
+        T.cmap_first.push_back((int32_t)first);
+        T.cmap_coef.resize(16 * (first + (size_t)n * n));
+        for (int j = 0; j < n; j++) for (int i = 0; i < n; i++) {
+            double Fm[4][4];   // rows: f(i), f(i+1), ft(i), ft(i+1); columns: the same along j
+            for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) {
+                const size_t k = idx(i + a, j + b);
+                Fm[a][b] = E[k]; Fm[a + 2][b] = d1[k]; Fm[a][b + 2] = d2[k]; Fm[a + 2][b + 2] = d12[k];
+            }
+            double* c = T.cmap_coef.data() + 16 * (first + (size_t)i + (size_t)n * j);
+            for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) {
+                double v = 0.0;
+                for (int p = 0; p < 4; p++) for (int q = 0; q < 4; q++) v += M[a][p] * Fm[p][q] * M[b][q];
+                c[4 * a + b] = v;
+            }
+        }
+        first += (size_t)n * n; at += (size_t)n * n;
+    }
+}
+
 static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, const BluesSystemExt* ext) {
     if (ext) {   // alchemical_pme_treatment: what the exact treatment refuses, each with its reason
-        if (ext->struct_size != (int32_t)sizeof(BluesSystemExt)) E_FAIL(h, "BluesSystemExt: struct_size %d does not match this library's %d", ext->struct_size, (int)sizeof(BluesSystemExt));
+        if (ext->struct_size != (int32_t)sizeof(BluesSystemExt) && ext->struct_size != BLUES_SYSTEM_EXT_SIZE_V1) E_FAIL(h, "BluesSystemExt: struct_size %d matches neither this library's %d nor %d (a caller from before the CMAP fields)", ext->struct_size, (int)sizeof(BluesSystemExt), BLUES_SYSTEM_EXT_SIZE_V1);
         const int tr = ext->alchemical_pme_treatment;
         if (tr != BLUES_ALCH_PME_DIRECT_SPACE && tr != BLUES_ALCH_PME_EXACT) E_FAIL(h, "alchemical_pme_treatment %d: the engine knows 0 ('direct-space') and 1 ('exact')", tr);
         if (tr == BLUES_ALCH_PME_EXACT) {
@@ -3519,6 +3621,25 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
             if (it->measure_shadow_work || it->measure_heat) E_FAIL(h, "alchemical_pme_treatment 'exact' together with measure_shadow_work / measure_heat is not supported: the energy ledger's device-side energy sum does not know the exact treatment's partials");
             if (it->switching_mode != BLUES_SWITCH_NONE) E_FAIL(h, "alchemical_pme_treatment 'exact' with a switching_mode integrator is not supported: its force and energy bookkeeping does not know the exact treatment's terms");
             h->pme_exact = s->n_alchemical > 0;   // (no alchemical atom: both treatments are the plain System)
+        }
+    }
+    // CMAP torsion maps (a caller of struct_size 8 has none): what such a System is refused for, each with its reason
+    const bool with_cmap = ext && ext->struct_size == (int32_t)sizeof(BluesSystemExt) && (ext->n_cmap_maps != 0 || ext->n_cmap_torsions != 0);
+    size_t cmap_values = 0;
+    if (with_cmap) {
+        if (ext->n_cmap_maps < 0 || ext->n_cmap_torsions < 0) E_FAIL(h, "CMAP: %d maps and %d torsions", ext->n_cmap_maps, ext->n_cmap_torsions);
+        if ((ext->n_cmap_maps > 0 && (!ext->cmap_size || !ext->cmap_energy)) || (ext->n_cmap_torsions > 0 && (!ext->cmap_torsion_map || !ext->cmap_torsion_atoms))) E_FAIL(h, "CMAP maps or torsions without their arrays");
+        for (int m = 0; m < ext->n_cmap_maps; m++) {
+            const int nn = ext->cmap_size[m];
+            if (nn < BLUES_CMAP_MIN_SIZE || nn > BLUES_CMAP_MAX_SIZE) E_FAIL(h, "CMAP map %d: size %dx%d; a map is n x n with n from %d to %d", m, nn, nn, BLUES_CMAP_MIN_SIZE, BLUES_CMAP_MAX_SIZE);
+            for (int q = 0; q < nn * nn; q++) if (!std::isfinite(ext->cmap_energy[cmap_values + q])) E_FAIL(h, "CMAP map %d: an energy is not finite", m);
+            cmap_values += (size_t)nn * nn;
+        }
+        for (int t = 0; t < ext->n_cmap_torsions; t++) {
+            if (ext->cmap_torsion_map[t] < 0 || ext->cmap_torsion_map[t] >= ext->n_cmap_maps) E_FAIL(h, "CMAP torsion %d: map %d of %d", t, ext->cmap_torsion_map[t], ext->n_cmap_maps);
+            const int32_t* q = ext->cmap_torsion_atoms + 8 * (size_t)t;
+            for (int pl = 0; pl < 8; pl++) if (q[pl] < 0 || q[pl] >= s->n_atoms) E_FAIL(h, "CMAP torsion %d: atom index out of range", t);
+            for (int d = 0; d < 2; d++) for (int a = 0; a < 4; a++) for (int b = a + 1; b < 4; b++) if (q[4 * d + a] == q[4 * d + b]) E_FAIL(h, "CMAP torsion %d: two equal atoms within one dihedral", t);
         }
     }
     if (gb && gb->model != BLUES_GB_NONE) {   // implicit solvent (kernels_gb.h): what such an engine refuses, each with its reason
@@ -3595,10 +3716,19 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
         mix(s->mass, sizeof(double) * n); mix(s->charge, sizeof(double) * n); mix(s->sigma, sizeof(double) * n); mix(s->epsilon, sizeof(double) * n);
         mix(s->exclusions, sizeof(int32_t) * 2 * (size_t)s->n_exclusions); mix(s->alchemical_atoms, sizeof(int32_t) * (size_t)s->n_alchemical);
         mix(s->bond_atoms, sizeof(int32_t) * 2 * (size_t)s->n_bonds); mix(s->constraint_atoms, sizeof(int32_t) * 2 * (size_t)s->n_constraints);
+        if (with_cmap) {   // (a System without maps keeps the key it had)
+            const int32_t cc[2] = {ext->n_cmap_maps, ext->n_cmap_torsions};
+            mix(cc, sizeof cc); mix(ext->cmap_size, sizeof(int32_t) * (size_t)ext->n_cmap_maps); mix(ext->cmap_energy, sizeof(double) * cmap_values);
+            mix(ext->cmap_torsion_map, sizeof(int32_t) * (size_t)ext->n_cmap_torsions); mix(ext->cmap_torsion_atoms, sizeof(int32_t) * 8 * (size_t)ext->n_cmap_torsions);
+        }
         std::lock_guard<std::mutex> lk(mu);
         auto it = known.find(key);
         if (it != known.end()) h->T = it->second.lock();
         if (h->T && ((int)h->T->mass.size() != n || (int)h->T->link_pairs.size() != 2 * (s->n_bonds + s->n_constraints))) h->T.reset();   // (a hash collision: build afresh, share nothing)
+        if (h->T && (with_cmap ? !(h->T->cmap_size == std::vector<int32_t>(ext->cmap_size, ext->cmap_size + ext->n_cmap_maps) && h->T->cmap_energy == std::vector<double>(ext->cmap_energy, ext->cmap_energy + cmap_values)
+                                   && h->T->cmap_tor_map == std::vector<int32_t>(ext->cmap_torsion_map, ext->cmap_torsion_map + ext->n_cmap_torsions)
+                                   && h->T->cmap_tor_atoms == std::vector<int32_t>(ext->cmap_torsion_atoms, ext->cmap_torsion_atoms + 8 * (size_t)ext->n_cmap_torsions))
+                                : !(h->T->cmap_size.empty() && h->T->cmap_tor_map.empty()))) h->T.reset();
         if (!h->T) {
             auto T = std::make_shared<HostTopology>();
             T->mass.assign(s->mass, s->mass + n); T->charge.assign(s->charge, s->charge + n); T->sigma.assign(s->sigma, s->sigma + n); T->eps.assign(s->epsilon, s->epsilon + n);
@@ -3612,6 +3742,11 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
             for (size_t a = 0; a < h->alch.size(); a++) T->alch_local[h->alch[a]] = (int)a;
             T->qn = T->charge; for (int a : h->alch) T->qn[a] = 0.0;
             T->link_pairs.assign(s->bond_atoms, s->bond_atoms + 2 * (size_t)s->n_bonds); T->link_pairs.insert(T->link_pairs.end(), s->constraint_atoms, s->constraint_atoms + 2 * (size_t)s->n_constraints);
+            if (with_cmap) {
+                T->cmap_size.assign(ext->cmap_size, ext->cmap_size + ext->n_cmap_maps); T->cmap_energy.assign(ext->cmap_energy, ext->cmap_energy + cmap_values);
+                T->cmap_tor_map.assign(ext->cmap_torsion_map, ext->cmap_torsion_map + ext->n_cmap_torsions); T->cmap_tor_atoms.assign(ext->cmap_torsion_atoms, ext->cmap_torsion_atoms + 8 * (size_t)ext->n_cmap_torsions);
+                cmap_tables(*T);
+            }
             h->T = T; known[key] = T;
             for (auto q = known.begin(); q != known.end();) { if (q->second.expired()) q = known.erase(q); else ++q; }
         }
@@ -4472,6 +4607,27 @@ int blues_get_stats(BluesEngine* h, int64_t stats[BLUES_N_STATS]) {
         std::vector<int> pc, ta;
         try { h->d_pcount.download(pc); h->d_tile_atoms.download(ta); for (size_t q = 0; q < pc.size() && q < ta.size(); q++) if (ta[q] >= 0) { stats[17] += pc[q]; stats[18] += (pc[q] + 63) / 64; } } catch (std::string&) {}
     }
+    return 0;
+}
+
+__global__ void k_cmap_angles(BondedArgs B, double* out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B.n_cmap) return;
+    CmapDihedral D;
+    cmap_dihedral(B, B.cmap_atoms + 8 * t, D); out[2 * t] = D.phi;
+    cmap_dihedral(B, B.cmap_atoms + 8 * t + 4, D); out[2 * t + 1] = D.phi;
+}
+int blues_get_cmap_angles(BluesEngine* h, double* out) {
+    if (h->n_cmap <= 0) return 0;
+    if (!out) E_FAIL(h, "blues_get_cmap_angles: no output array");
+    if (!h->have_positions) E_FAIL(h, "blues_get_cmap_angles: no positions set");
+    HIP_OK(h, hipSetDevice(h->device));
+    if (flush_program(h)) return 1;
+    hipLaunchKernelGGL(k_cmap_angles, dim3((h->n_cmap + 127) / 128), dim3(128), 0, h->stream, make_bonded_args(h), h->d_cmap_angles.p);
+    h->st_launches++;
+    HIP_OK(h, hipGetLastError());
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    HIP_OK(h, hipMemcpy(out, h->d_cmap_angles.p, sizeof(double) * 2 * h->n_cmap, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -258,11 +258,11 @@ __global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32_b(const R
     alchemical_dense32_body<MASK>(A);
 }
 
-template <bool CENT = false>
+template <bool CENT = false, bool CMAP = false>
 __global__ void __launch_bounds__(128) k_bonded_entries_b(const RepCore* __restrict__ reps, BondedDyn d) {
     if (!reps[blockIdx.y].active) return;
     BondedArgs B = reps[blockIdx.y].bo; apply_dyn(B, d, reps[blockIdx.y].draw_delta);
-    bonded_entries_body<CENT>(B, blockIdx.x, 128);
+    bonded_entries_body<CENT, CMAP>(B, blockIdx.x, 128);
 }
 
 template <bool LEAN>
@@ -418,11 +418,11 @@ __global__ void k_zero_acc_b(DevAccum* const* __restrict__ acc, int R) {
     if (r < R && acc[r]) { DevAccum z; z.protocol_work = z.dE_last = z.shadow_work = z.u_open = 0.0; z.heat = acc[r]->heat; z.e_slot[0] = z.e_slot[1] = z.e_slot[2] = 0.0; *acc[r] = z; }   // (heat survives a reset, as in the oracle; 0 where it is not measured)
 }
 
-template <bool CENT = false>
+template <bool CENT = false, bool CMAP = false>
 __global__ void __launch_bounds__(256) k_bonded_energy_b(const RepCore* __restrict__ reps) {
     if (!reps[blockIdx.y].active) return;
     const BondedArgs B = reps[blockIdx.y].bo;
-    bonded_energy_body<CENT>(B);
+    bonded_energy_body<CENT, CMAP>(B);
 }
 
 // kinetic energy of every member: one block each, fixed summation order -> ke[r]

@@ -1,5 +1,5 @@
 // kernels_bonded.h -- harmonic bonds/angles, periodic torsions, env-env 1-4 exceptions, the
-// positional restraint and harmonic centroid bonds (K3/K4), fp64, gather form.
+// positional restraint, harmonic centroid bonds and CMAP torsion correction maps (K3/K4), fp64, gather form.
 //
 // OpenMM's HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce / NonbondedForce
 // exceptions / CustomExternalForce('k_restr*periodicdistance(x,y,z,x0,y0,z0)^2',
@@ -16,6 +16,10 @@ enum { T_BOND = 0, T_ANGLE = 1, T_TORSION = 2, T_EXC = 3, T_RESTR = 4, T_EWEX = 
 // templates below know it -- the CENT = false ones, which every System without such bonds runs, are the code they were before it existed.
 enum { T_CENT = T_NTYPES };   // (the first value past the per-type arrays; blues_engine.hip asserts it stays there)
 #define CENT_GROUP 8   // places per group (BLUES_MAX_CENTROID_GROUP); a term is two groups, unused places hold atom -1 and weight 0
+// CMAP torsions (OpenMM's CMAPTorsionForce: a tabulated energy over two dihedrals, bicubic patches): the second ENTRY-only type, on any
+// System.  Terms in arrays of their own (BondedArgs::cmap_*), energy booked with the torsions', known to the CMAP = true instantiations only.
+enum { T_CMAP = T_NTYPES + 1 };
+#define CMAP_TWO_PI 6.283185307179586476925286766559
 
 struct BondedArgs {
     int n_rows;
@@ -44,6 +48,9 @@ struct BondedArgs {
     int n_entry_blocks;
     // centroid bonds: 2 * CENT_GROUP atoms and 2 * CENT_GROUP weights + k per term
     int n_cent; const int* cent_atoms; const double* cent_params;
+    // CMAP torsions: 8 atoms per term; cmap_grid[2 t] = n of the term's map, [2 t + 1] = its first patch in cmap_coef, which holds 16
+    // doubles per patch (i + n * j): c[a][b] of E = sum c[a][b] t^a u^b, t = phi / delta - i, u = psi / delta - j
+    int n_cmap; const int* cmap_atoms; const int* cmap_grid; const double* cmap_coef;
 };
 
 __device__ inline void mi3(const BondedArgs& B, double d[3]) {
@@ -54,10 +61,69 @@ __device__ inline void cross3(const double a[3], const double b[3], double c[3])
 }
 __device__ inline double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// ---- CMAP: the dihedral of T_TORSION below (same vectors, sign rule and minimum image) shifted into [0, 2 pi], with what its
+// position gradient needs
+struct CmapDihedral { double m[3], nn[3], m2, n2, lkj, p, qq, phi; };
+__device__ inline void cmap_dihedral(const BondedArgs& B, const int* q, CmapDihedral& D) {
+    double rij[3], rkj[3], rkl[3];
+    for (int c = 0; c < 3; c++) { rij[c] = B.x[c][q[0]] - B.x[c][q[1]]; rkj[c] = B.x[c][q[2]] - B.x[c][q[1]]; rkl[c] = B.x[c][q[2]] - B.x[c][q[3]]; }
+    mi3(B, rij); mi3(B, rkj); mi3(B, rkl);
+    cross3(rij, rkj, D.m); cross3(rkj, rkl, D.nn);
+    D.m2 = dot3(D.m, D.m); D.n2 = dot3(D.nn, D.nn);
+    const double lkj2 = dot3(rkj, rkj);
+    D.lkj = sqrt(lkj2);
+    // T_TORSION's angle -- cos = m.n / |m||n|, negative where rij.n < 0 -- taken as atan2(|rkj| rij.n, m.n): the same angle with the same
+    // sign rule, but acos loses half its digits near 0 and pi (1e-8 rad), and here the angle picks the patch and the place within it
+    const double phi = atan2(D.lkj * dot3(rij, D.nn), dot3(D.m, D.nn));
+    D.phi = phi < 0.0 ? phi + CMAP_TWO_PI : phi;
+    D.p = dot3(rij, rkj) / lkj2; D.qq = dot3(rkl, rkj) / lkj2;
+}
+// F += -ddphi * d(phi)/d(x of the atom in `role`): T_TORSION's fi, fl, sv expressions
+__device__ inline void cmap_project(const CmapDihedral& D, const double ddphi, const int role, double F[3]) {
+    for (int c = 0; c < 3; c++) {
+        const double fi = -ddphi * D.lkj / D.m2 * D.m[c], fl = ddphi * D.lkj / D.n2 * D.nn[c];
+        const double sv = D.p * fi - D.qq * fl;
+        F[c] += role == 0 ? fi : (role == 1 ? -(fi - sv) : (role == 2 ? -(fl + sv) : fl));
+    }
+}
+// patch index and local coordinate of an angle in [0, 2 pi] (-tiny + 2 pi rounds to 2 pi: patch n - 1 at t = 1, which continues patch 0 at t = 0)
+__device__ inline int cmap_patch(const double ang, const int n, double* t) {
+    const double s = ang * ((double)n / CMAP_TWO_PI);
+    int i = (int)s; i = i > n - 1 ? n - 1 : (i < 0 ? 0 : i);
+    *t = s - (double)i;
+    return i;
+}
+__device__ inline double cmap_term(const BondedArgs& B, const int idx, const int role, double F[3]) {
+    const int* q = B.cmap_atoms + 8 * idx;
+    const int n = B.cmap_grid[2 * idx];
+    CmapDihedral A, C;
+    cmap_dihedral(B, q, A); cmap_dihedral(B, q + 4, C);
+    double t, u;
+    const int i = cmap_patch(A.phi, n, &t), j = cmap_patch(C.phi, n, &u);
+    // the patch's 16 coefficients lie together, 128 B on a 128 B boundary: four 32 B loads
+    const double4* cp = reinterpret_cast<const double4*>(B.cmap_coef + 16 * ((size_t)B.cmap_grid[2 * idx + 1] + (size_t)(i + n * j)));
+    double e = 0.0, et = 0.0, eu = 0.0;
+    for (int a = 3; a >= 0; a--) {   // Horner in t over rows r_a(u) = sum_b c[a][b] u^b, with d/dt and d/du carried along
+        const double4 c = cp[a];
+        const double r = ((c.w * u + c.z) * u + c.y) * u + c.x, ru = (3.0 * c.w * u + 2.0 * c.z) * u + c.y;
+        et = et * t + e; e = e * t + r; eu = eu * t + ru;
+    }
+    if (role >= 0) {   // the entry's atom may sit in both dihedrals (Amber's five-atom form): every place that names it, in place order
+        const double scale = (double)n / CMAP_TWO_PI;
+        const int me = q[role];
+        for (int pl = 0; pl < 8; pl++)
+            if (q[pl] == me) cmap_project(pl < 4 ? A : C, (pl < 4 ? et : eu) * scale, pl & 3, F);
+    }
+    return e;
+}
+
 // energy of term (type, idx); if role >= 0 also the force on the atom in that role
-template <bool CENT = false>
+template <bool CENT = false, bool CMAP = false>
 __device__ inline double bonded_term(const BondedArgs& B, int type, int idx, int role, double F[3]) {
     F[0] = F[1] = F[2] = 0.0;
+    if constexpr (CMAP) {
+        if (type == T_CMAP) return cmap_term(B, idx, role, F);
+    }
     if constexpr (CENT) {
         if (type == T_CENT) {  // E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w): explicit weights, summed in the groups' order; never periodic
             const int* q = B.cent_atoms + 2 * CENT_GROUP * idx;
@@ -170,7 +236,7 @@ __device__ inline double bonded_term(const BondedArgs& B, int type, int idx, int
 // one thread per (row, entry): the force of one term on one of its mobile atoms -> fent[3][n_entries];
 // blocks past n_entry_blocks draw the N(0,1) numbers of the coming O substeps (counter-based, so they can be
 // produced before the velocities they will be applied to exist).
-template <bool CENT = false>
+template <bool CENT = false, bool CMAP = false>
 __device__ __forceinline__ void bonded_entries_body(const BondedArgs& B, const int block_id, const int nthreads) {
     if (block_id >= B.n_entry_blocks) {
         const int g = (block_id - B.n_entry_blocks) * nthreads + threadIdx.x;
@@ -184,16 +250,17 @@ __device__ __forceinline__ void bonded_entries_body(const BondedArgs& B, const i
     const int e = block_id * nthreads + threadIdx.x;
     if (e >= B.n_entries) return;
     double F[3];
-    bonded_term<CENT>(B, B.ent_type[e], B.ent_term[e], B.ent_role[e], F);
+    bonded_term<CENT, CMAP>(B, B.ent_type[e], B.ent_term[e], B.ent_role[e], F);
     B.fent[e] = F[0]; B.fent[B.n_entries + e] = F[1]; B.fent[2 * B.n_entries + e] = F[2];
 }
 
-template <bool CENT = false>
-__global__ void __launch_bounds__(128) k_bonded_entries(BondedArgs B) { bonded_entries_body<CENT>(B, blockIdx.x, 128); }
+template <bool CENT = false, bool CMAP = false>
+__global__ void __launch_bounds__(128) k_bonded_entries(BondedArgs B) { bonded_entries_body<CENT, CMAP>(B, blockIdx.x, 128); }
 
 // energy of every term (frozen ones included): per-block partial sums per type
-// (CENT: the centroid bonds follow the six types; their energy goes into the restraint's partial -- both are energy term 7)
-template <bool CENT = false>
+// (CENT: the centroid bonds follow the six types; their energy goes into the restraint's partial -- both are energy term 7;
+//  CMAP: the CMAP torsions follow those; their energy goes into the torsions' partial -- both are energy term 2)
+template <bool CENT = false, bool CMAP = false>
 __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
     const int gid = blockIdx.x * 256 + threadIdx.x;
     double e[T_NTYPES] = {0, 0, 0, 0, 0, 0};
@@ -206,6 +273,11 @@ __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
     if constexpr (CENT) {
         const int idx = gid - base;
         if (idx >= 0 && idx < B.n_cent) { double F[3]; e[T_RESTR] += bonded_term<true>(B, T_CENT, idx, -1, F); }
+        base += B.n_cent;
+    }
+    if constexpr (CMAP) {
+        const int idx = gid - base;
+        if (idx >= 0 && idx < B.n_cmap) { double F[3]; e[T_TORSION] += cmap_term(B, idx, -1, F); }
     }
     __shared__ double s[4][T_NTYPES];
     for (int ty = 0; ty < T_NTYPES; ty++) { double v = wave_sum(e[ty]); if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6][ty] = v; }
@@ -213,5 +285,5 @@ __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
     if (threadIdx.x < T_NTYPES) B.epart[blockIdx.x * T_NTYPES + threadIdx.x] = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x];
 }
 
-template <bool CENT = false>
-__global__ void __launch_bounds__(256) k_bonded_energy(BondedArgs B) { bonded_energy_body<CENT>(B); }
+template <bool CENT = false, bool CMAP = false>
+__global__ void __launch_bounds__(256) k_bonded_energy(BondedArgs B) { bonded_energy_body<CENT, CMAP>(B); }

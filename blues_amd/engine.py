@@ -26,6 +26,7 @@ class NativeEngine:
             system.check_custom_forces()
             system.check_implicit_solvent(integrator)
             system.check_alchemical_pme_treatment(integrator)
+            system.check_cmap()
         except ValueError as e:
             raise EngineError(str(e))
         self._lib = load()
@@ -38,6 +39,11 @@ class NativeEngine:
             if not hasattr(self._lib, "blues_engine_create_ext"):
                 raise EngineError("alchemical_pme_treatment %r needs blues_engine_create_ext, which this library does not have: rebuild it "
                                   "(python -m blues_amd.build)" % (system.alchemical_pme_treatment,))
+            # (a library from before the maps would refuse the descriptor's size; one without this entry is such a library)
+            if system.has_cmap and not hasattr(self._lib, "blues_get_cmap_angles"):
+                raise EngineError("a System with CMAP maps needs blues_get_cmap_angles (and the CMAP fields of BluesSystemExt), which this "
+                                  "library does not have: rebuild it (python -m blues_amd.build)")
+            self._keep_e = ext
             gd = None
             if system.implicit_solvent is not None:
                 gd, self._keep_g = system.implicit_solvent.to_desc()
@@ -219,6 +225,17 @@ class NativeEngine:
                 "max_jcount": s[8], "resorts": s[9], "list_builds": s[10], "own_energy_evaluations": s[11],
                 "nonbonded_kernel": s[12], "tiles_per_list": s[13], "atom_list_entries": s[14], "atom_list_iterations": s[15],
                 "atom_prunes": s[16], "pruned_list_entries": s[17], "pruned_list_iterations": s[18], "pruned_lists": s[19], "alchemical_kernel": s[20], "step_threads": s[21]}
+
+    def cmap_angles(self):
+        """(phi, psi) of every CMAP torsion at the current device positions: (m, 2) radians in [0, 2 pi)."""
+        m = len(np.asarray(self.system.cmap_torsions).reshape(-1, 9))
+        out = np.zeros((m, 2))
+        if m == 0:
+            return out
+        if not hasattr(self._lib, "blues_get_cmap_angles"):
+            raise EngineError("cmap_angles needs blues_get_cmap_angles, which this library does not have: rebuild it (python -m blues_amd.build)")
+        self._check(self._lib.blues_get_cmap_angles(self._h, self._ptr(out)))
+        return out
 
     def time_nonbonded(self, reps=20):
         u = C.c_double(); self._check(self._lib.blues_time_nonbonded(self._h, int(reps), C.byref(u))); return u.value

@@ -33,6 +33,10 @@ def save_system(path, system: SystemData, **extra):
         d["alchemical_pme_treatment"] = np.asarray(system.alchemical_pme_treatment)
     if system.implicit_solvent is not None:
         d.update({"gb_" + k: np.asarray(getattr(system.implicit_solvent, k)) for k in _GB_FIELDS})
+    if system.has_cmap:   # (written only where there are some: files stay readable by earlier versions)
+        d["cmap_torsions"] = np.asarray(system.cmap_torsions, dtype=np.int32).reshape(-1, 9)
+        d["cmap_n_maps"] = np.asarray(len(system.cmap_maps), dtype=np.int32)
+        d.update({"cmap_map_%d" % k: np.asarray(m, dtype=np.float64) for k, m in enumerate(system.cmap_maps)})
     d.update({k: np.asarray(v) for k, v in extra.items()})
     np.savez_compressed(path, **d)
 
@@ -53,7 +57,10 @@ def load_system(path):
                                                      float(z["gb_solvent_dielectric"]), float(z["gb_surface_area_energy"]))
     if "alchemical_pme_treatment" in z.files:   # (older files: "direct-space", the field's default)
         kw["alchemical_pme_treatment"] = str(z["alchemical_pme_treatment"].item())
-    extra = {k: z[k] for k in z.files if k not in kw and not k.startswith("gb_")}
+    if "cmap_n_maps" in z.files:
+        kw["cmap_maps"] = tuple(z["cmap_map_%d" % k] for k in range(int(z["cmap_n_maps"])))
+        kw["cmap_torsions"] = z["cmap_torsions"]
+    extra = {k: z[k] for k in z.files if k not in kw and not k.startswith("gb_") and not k.startswith("cmap_")}
     return SystemData(**kw), extra
 
 
@@ -189,7 +196,15 @@ def tile_system(system: SystemData, reps):
         names=None if system.names is None else list(system.names) * ncopy,
         implicit_solvent=None if system.implicit_solvent is None else system.implicit_solvent.subset(np.tile(np.arange(n), ncopy)),
         alchemical_pme_treatment=system.alchemical_pme_treatment,
+        cmap_maps=tuple(system.cmap_maps or ()), cmap_torsions=_tile_cmap_torsions(system.cmap_torsions, n, ncopy),
     )
+
+
+def _tile_cmap_torsions(torsions, n, ncopy):
+    """every copy keeps the map (column 0) and moves its eight atoms"""
+    t = np.asarray(torsions, dtype=np.int32).reshape(-1, 9)
+    shift = np.array([0] + [1] * 8, dtype=np.int32)
+    return np.concatenate([t + c * n * shift for c in range(ncopy)], axis=0).astype(np.int32)
 
 
 def toluene_box():

@@ -213,12 +213,34 @@ int blues_engine_create_gb(const BluesSystemDesc *sys, const BluesIntegratorDesc
  * by box constants only: there is no mesh differential to take).  A batch may not mix treatments. */
 #define BLUES_ALCH_PME_DIRECT_SPACE 0
 #define BLUES_ALCH_PME_EXACT 1
+/* CMAP torsion correction maps: OpenMM's CMAPTorsionForce, what createSystem adds for a prmtop with CMAP_* / CHARMM_CMAP_* sections
+ * (Amber ff19SB, CHARMM through chamber; reference blues/simulation.py:139-219).  Additive to ABI 9.
+ *   map      n x n energies (kJ/mol), 4 <= n <= 64; E[i, j] belongs to phi = 2 pi i / n, psi = 2 pi j / n and is stored energy[i + n * j];
+ *   torsion  a map and eight atoms a1..a4, b1..b4: phi is the dihedral of a1..a4, psi that of b1..b4, each exactly the dihedral of a
+ *            periodic torsion (same vectors, sign and minimum image), shifted into [0, 2 pi).
+ * With d = 2 pi / n, d1 / d2 the knot derivatives of the periodic C2 cubic splines through the map along i / j and d12 those of the
+ * spline through d1 along j, the energy within patch (floor(phi / d), floor(psi / d)) (both clamped to n - 1, indices wrapping at the
+ * seam) is the bicubic Hermite patch through E, d1, d2, d12 at its four corners.  The term is not alchemical: it is the same in all
+ * three lambda slots, adds nothing to protocol work and is booked with energy term [2].  Creation fails, with the reason, for n outside
+ * 4..64, a torsion that names a missing map or atom, two equal atoms within one dihedral, and a map value that is not finite. */
+#define BLUES_CMAP_MIN_SIZE 4
+#define BLUES_CMAP_MAX_SIZE 64
+#define BLUES_SYSTEM_EXT_SIZE_V1 8      /* struct_size of a caller from before the CMAP fields: it has no maps */
 typedef struct BluesSystemExt {
-    int32_t struct_size;                 /* sizeof(BluesSystemExt) of the caller */
+    int32_t struct_size;                 /* sizeof(BluesSystemExt) of the caller: 8 (a caller from before the maps: none) or this struct's */
     int32_t alchemical_pme_treatment;    /* BLUES_ALCH_PME_* */
+    int32_t n_cmap_maps;
+    const int32_t *cmap_size;            /* [n_cmap_maps] n of every map */
+    const double *cmap_energy;           /* the maps one after another, n * n values each */
+    int32_t n_cmap_torsions;
+    const int32_t *cmap_torsion_map;    /* [n_cmap_torsions] */
+    const int32_t *cmap_torsion_atoms;   /* [8 * n_cmap_torsions] a1..a4, b1..b4 */
 } BluesSystemExt;
 /* ext = NULL: blues_engine_create_gb */
 int blues_engine_create_ext(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, const BluesImplicitSolventDesc *gb, const BluesSystemExt *ext, int device, BluesEngine **out);
+/* (phi, psi) of every CMAP torsion at the engine's current device positions, radians in [0, 2 pi): what a Ramachandran reporter
+ * reads.  Additive to ABI 9; a library without it loads, and only a System with maps needs it. */
+int blues_get_cmap_angles(BluesEngine *h, double *out /* [n_cmap_torsions][2] */);
 int blues_engine_destroy(BluesEngine *h);
 const char *blues_last_error(const BluesEngine *h);
 int blues_abi_version(void);
