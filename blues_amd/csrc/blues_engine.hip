@@ -333,6 +333,9 @@ struct BluesEngine {
     // kept superset of every group list's candidates (kernels_nb.h: build_lists_body): buffers sized by the layout; sup_slack: ListArgs.sup_slack
     // (nm; <= 0: every rebuild scans all atoms).  Development switch: blues_set_global "group_list_superset"
     DBuf<int> d_sup, d_sup_stat; DBuf<SupHdr> d_sup_hdr; int sup_cap = 0; float sup_slack = 0.3f;
+    // Coulomb-only walk of the per-atom-list kernel for i-atoms without epsilon (kernels_nb.h: nonbonded_atom_body): NbArgs.coulomb_walk.
+    // Development switch: blues_set_global "nb_coulomb_walk"; n_eps0_islots: the i-slots of the current layout whose atom has none (sort_and_tile)
+    bool nb_coulomb_walk = true; int n_eps0_islots = 0;
     float alist_pf_reach = 0.8f;   // ListArgs.pf_reach (nm): the reach up to which a wave of the atoms'-list builder prefilters its group's list; < 0: never.  Development switch: blues_set_global "atom_list_prefilter"
     int n_entries = 0;
     int int_blocks = 1, int_threads = 128;
@@ -1089,6 +1092,8 @@ static int sort_and_tile(BluesEngine* h) {
         const int o = h->h_orig_of_sorted[s];
         if (h->T->mass[o] != 0.0 && h->T->alch_local[o] < 0) { islot[o] = (int)tile_atoms.size(); tile_atoms.push_back(s); }
     }
+    h->n_eps0_islots = 0;   // (what the per-atom-list kernel tests: the image's fp32 2 sqrt(eps) is zero)
+    for (int s : tile_atoms) if ((float)(2.0 * std::sqrt(h->T->eps[h->h_orig_of_sorted[s]])) == 0.0f) h->n_eps0_islots++;
     h->n_itiles = ((int)tile_atoms.size() + 63) / 64;
     tile_atoms.resize((size_t)h->n_itiles * 64, -1);
     if (!h->alch.empty()) { for (size_t a = 0; a < 64; a++) tile_atoms.push_back(a < h->alch.size() ? h->h_sorted_of_orig[h->alch[a]] : -1); }
@@ -1681,7 +1686,7 @@ template <typename R> static NbArgs<R> make_nb_args(BluesEngine* h) {
         }
         a.pimg4 = h->d_pimg4.p; a.pimg2 = h->d_pimg2.p; a.mlist = h->d_mlist.p; a.mcount = h->d_mcount.p; a.mcap = h->mcap; a.aself = h->d_aself.p;   // (the kernel always stages the packed image: it holds the ghost record the lists are padded with)
     }
-    a.S = h->S; a.n_lists = h->n_lists;
+    a.S = h->S; a.n_lists = h->n_lists; a.coulomb_walk = h->nb_coulomb_walk ? 1 : 0;
     return a;
 }
 
@@ -4497,6 +4502,9 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
         if (h->d_sup_stat.p) HIP_OK(h, hipMemcpy(st, h->d_sup_stat.p, sizeof st, hipMemcpyDeviceToHost));   // (no layout has made room for supersets yet: 0, 0)
         *value = st[k == "group_list_superset_served" ? 0 : 1];
     }
+    // i-slots of the current layout whose atom takes the per-atom-list kernel's Coulomb-only walk: those without epsilon (0 with the switch
+    // off, with another nonbonded kernel, or where the kernel evaluates the erfc/exp form, which keeps the full walk)
+    else if (k == "nb_coulomb_walk_atoms") *value = (h->nb_coulomb_walk && h->k1_mode == 2 && !h->ewpoly.exact) ? h->n_eps0_islots : 0;
     else if (k == "shadow_work") {
         if (h->switch_mode != BLUES_SWITCH_NONE) *value = h->sw_shadow;
         else if (h->led_flags & LED_SHADOW) { if (read_acc(h, &a)) return 1; *value = a.shadow_work; }
@@ -4546,6 +4554,10 @@ int blues_set_global(BluesEngine* h, const char* name, double value) {
     // takes the direct walk; N > 0: waves whose atoms lie within N picometres of their centre prefilter their group's list (default
     // 800: scripts/census_atom_list_prefilter.py).  The lists are the same either way; the Python loader maps BLUES_ATOM_LIST_PREFILTER onto it
     if (k == "atom_list_prefilter") { h->alist_pf_reach = value <= 0.0 ? -1.0f : (float)(std::min(value, 1e5) * 1e-3); return 0; }
+    // development switch of the per-atom-list kernel (kernels_nb.h: nonbonded_atom_body), not an integrator variable: 0: every i-atom walks
+    // its list with the full pair body; 1 (default): an i-atom without epsilon takes the Coulomb-only walk.  The forces are the same bits
+    // either way; the Python loader maps BLUES_NB_COULOMB_WALK onto it at creation
+    if (k == "nb_coulomb_walk") { if (flush_program(h)) return 1; h->nb_coulomb_walk = value != 0.0; h->args_epoch++; return 0; }
     if (k == "protocol_work" || (k == "shadow_work" && (h->led_flags & LED_SHADOW)) || (k == "heat" && (h->led_flags & LED_HEAT))) {
         DevAccum a; if (read_acc(h, &a)) return 1;
         if (k == "protocol_work") a.protocol_work = value; else if (k == "heat") a.heat = value; else a.shadow_work = value;

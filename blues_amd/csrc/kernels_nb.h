@@ -674,6 +674,7 @@ template <typename R> struct NbArgs {
     // pruned; pneed[islot] != 0: stale (ListArgs); xprune[k][islot]: where the atom was then (fixed point, as in the image)
     unsigned short* plist; int* pcount; int* pneed; unsigned* xprune[3];
     const uint4* pimg4; const float2* pimg2; const int* mlist; const int* mcount; int mcap;   // packed group images (ListArgs)
+    int coulomb_walk;              // nonbonded_atom_body: != 0: an i-atom without epsilon takes the Coulomb-only walk (blues_set_global "nb_coulomb_walk")
     const unsigned short* aself;   // (ListArgs)
 };
 
@@ -886,6 +887,16 @@ __global__ void __launch_bounds__(256) k_nonbonded_sub(NbArgs<float> a, NbConst<
 // BUILD (the packed image keeps it) is within cutoff + trig + m of that position: until the next rebuild the candidate stays
 // within `trig` of its build position whatever prunes it goes through itself.  (Round 3's first rule measured mobile
 // candidates from their current position and lost pairs at the cutoff: blues_audit_lists.)
+// Coulomb-only walk.  An i-atom without epsilon (2 sqrt(eps) = 0 in its own record: a water's hydrogen, two i-atoms in three on the
+// benchmark) has tt = (se_i se_j) s6 = 0 and flj = +-0 with every entry of its list.  Its wave -- one scalar compare per atom turn on
+// the record every lane has just read, beside the pruning / exact dispatch -- walks the list with a pair body that has no sig / s2 /
+// s6 / tt / flj and takes fs = (q_i q_j) g: the value fma(q_i q_j, g, +-0) rounds to whenever it is not zero; where it is zero (the
+// ghost, an uncharged atom) only the zero's sign can differ, and it is added to partial sums that start at +0 -- the stored force is
+// the same bits (an overlap, r2 = 0, is NaN both ways).  Where such a walk does not prune, nothing reads the entry's {sigma/2, 2 sqrt(eps)}
+// record and its DS read is not issued (the pruning walk keeps it for the sign of sigma/2, "j is mobile").  Per chunk of a straight-line
+// group: 33 VALU instructions and one DS read instead of 43 and two.  The force kernel's polynomial form only: six
+// walks ({prune} x {LJ} and the two erfc/exp walks), 51 KB of code; the energy kernel is the one it was.  NbArgs.coulomb_walk = 0
+// (blues_set_global "nb_coulomb_walk"): every atom takes the full walk.
 template <bool ENERGY>
 __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, const NbConst<float>& c, const AtomF* __restrict__ img, const int t) {   // t: list (group of S i-tiles)
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4))); typedef float f32x4 __attribute__((ext_vector_type(4))); typedef float f32x2 __attribute__((ext_vector_type(2)));   // (plain vector types: loads through an address-space pointer stay loads)
@@ -1025,6 +1036,13 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
     float k_rp2 = c.rp2, k_rp2m = c.rp2_m;   // (a select between two fields of the argument record becomes an indexed load from a scratch copy of it)
     NB_VREG(k_rp2); NB_VREG(k_rp2m);
     const bool exact = c.ew.exact != 0;   // (kernel argument: wave-uniform)
+    // (the Coulomb-only walk exists for the force kernel's polynomial form; NbArgs.coulomb_walk = 0: every atom takes the full walk)
+#if defined(K1X_EMPTY) || defined(K1X_NOPOLY) || defined(K1X_NOGATHER) || defined(K1X_NOCVT) || defined(K1X_NOLIST) || defined(K1X_NOREDUCE)
+    constexpr bool NB_COULOMB_WALK = false;   // (the floor experiments measure the full walk)
+#else
+    constexpr bool NB_COULOMB_WALK = !ENERGY;
+#endif
+    const bool coul_on = NB_COULOMB_WALK && a.coulomb_walk != 0 && !exact;   // (kernel-uniform)
     double elj = 0.0, ecl = 0.0;
     int s_nxt = wv;
     while (s_nxt < nslot) {
@@ -1040,6 +1058,10 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
         if (cnt < 0) continue;   // wave-uniform; empty slots are never read back (FinRec.atom < 0)
         // the atom itself: its record in the LDS image (same address in every lane: one broadcast read, no scalar round trip)
         const u32x4 me4 = *L3(const u32x4, (size_t)(2u * (unsigned)self + NB_LQ_BYTES)); const f32x2 me2 = *L3(const f32x2, (size_t)(unsigned)self);
+        // an atom without epsilon (a water's hydrogen: two i-atoms in three on the benchmark) has flj = +-0 with every entry: its wave
+        // takes the Coulomb-only walk.  One scalar compare per atom turn on the record every lane has just read
+        const float se_self = me2.y;   // (a copy: __builtin_bit_cast of a vector's component reads the vector's first one)
+        const bool coul = coul_on && __builtin_amdgcn_readfirstlane(__float_as_int(se_self)) == 0;   // wave-uniform
         unsigned ix = me4.x, iy = me4.y, iz = me4.z; float iq = __uint_as_float(me4.w), ihs = __builtin_fabsf(me2.x), ise = me2.y;
         NB_VREG(ix); NB_VREG(iy); NB_VREG(iz); NB_VREG(iq); NB_VREG(ihs); NB_VREG(ise);
         const bool pruning = !ENERGY && dual && stale;   // an energy evaluation reads whichever list is valid and writes none
@@ -1048,18 +1070,20 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
         int pcnt = 0;   // survivors written so far (wave-uniform)
         double fx = 0.0, fy = 0.0, fz = 0.0;
         float bx = 0.0f, by = 0.0f, bz = 0.0f;
-        auto fetch = [&](unsigned e, u32x4& q4, f32x2& q2) {
+        auto fetch = [&](unsigned e, u32x4& q4, f32x2& q2, auto lj_rec_tag) {
+            constexpr bool Q2 = decltype(lj_rec_tag)::value;   // false: nothing of the walk reads the {sigma/2, 2 sqrt(eps)} record -- one DS read per entry
             unsigned e2;   // (the compiler turns e + e into a shift, which issues at half the rate of the add)
             asm("v_add_u32 %0, %1, %1" : "=v"(e2) : "v"(e));
 #if defined(K1X_NOGATHER)  // (floor experiment: conflict-free, consecutive addresses)
             e2 = (unsigned)lane * 16u + (e2 & 0x3c00u); const unsigned e1 = (unsigned)lane * 8u + (e & 0x1e00u);
             q4 = *L3(const u32x4, (size_t)(e2 + NB_LQ_BYTES)); q2 = *L3(const f32x2, (size_t)e1);
 #else
-            q4 = *L3(const u32x4, (size_t)(e2 + NB_LQ_BYTES)); q2 = *L3(const f32x2, (size_t)e);   // (LDS addresses as numbers: the dynamic area starts at 0, checked below)
+            q4 = *L3(const u32x4, (size_t)(e2 + NB_LQ_BYTES));   // (LDS addresses as numbers: the dynamic area starts at 0, checked below)
+            if (Q2) q2 = *L3(const f32x2, (size_t)e); else q2 = f32x2{0.0f, 0.0f};   // (never read then)
 #endif
         };
-        auto pair = [&](unsigned e, const u32x4& q4, const f32x2& q2, auto write_tag, auto exact_tag) {
-            constexpr bool W = decltype(write_tag)::value, X = decltype(exact_tag)::value;
+        auto pair = [&](unsigned e, const u32x4& q4, const f32x2& q2, auto write_tag, auto exact_tag, auto lj_tag) {
+            constexpr bool W = decltype(write_tag)::value, X = decltype(exact_tag)::value, LJ = decltype(lj_tag)::value || ENERGY;
 #if defined(K1X_NOCVT)     // (floor experiment: wrong numbers, no conversions)
             const float dx = __uint_as_float(ix - q4.x) * k_sx, dy = __uint_as_float(iy - q4.y) * k_sy, dz = __uint_as_float(iz - q4.z) * k_sz;
 #else
@@ -1072,9 +1096,12 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
             const float r2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
             if (!ENERGY) {
                 const float inv_r = __builtin_amdgcn_rsqf(r2), inv_r2 = inv_r * inv_r;
-                const float sig = ihs + __builtin_fabsf(q2.x);
-                const float s2 = sig * sig * inv_r2, s6 = s2 * s2 * s2, tt = (ise * q2.y) * s6;
-                const float flj = tt * fmaf(12.0f, s6, -6.0f);
+                float flj = 0.0f;
+                if (LJ) {
+                    const float sig = ihs + __builtin_fabsf(q2.x);
+                    const float s2 = sig * sig * inv_r2, s6 = s2 * s2 * s2, tt = (ise * q2.y) * s6;
+                    flj = tt * fmaf(12.0f, s6, -6.0f);
+                }
                 float g;
                 if (X) {
                     const float ar = c.alpha * (r2 * inv_r), ex = __expf(-ar * ar);
@@ -1090,7 +1117,9 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
 #endif
                     g = fmaf(inv_r, inv_r2, -T);
                 }
-                float fs = fmaf(iq * jq, g, flj * inv_r2);
+                // LJ = false (an i-atom without epsilon: flj = +-0 for every entry): the plain product is what the FMA rounds to whenever
+                // it is not zero, and a zero of either sign adds the same to bx / by / bz, which start at +0 -- the same stored force
+                float fs = LJ ? fmaf(iq * jq, g, flj * inv_r2) : (iq * jq) * g;
                 float m;   // 1 inside the cutoff, 0 outside (the ghost and the margin entries): (rc^2 - r^2) 2^30 clamped to [0, 1]
                 asm("v_fma_f32 %0, %1, %2, %3 clamp" : "=v"(m) : "v"(r2), "v"(k_nbig), "v"(k_bigrc2));
                 fs *= m;
@@ -1128,38 +1157,46 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
         // is computed (sched_group_barrier pins that order), so the LDS latency is paid once per group.
         // The fp32 partials of a lane hold at most NB_ATOM_U pair terms before they are folded.
         const int nch = __builtin_amdgcn_readfirstlane((cnt + 63) >> 6);   // wave-uniform (and known to be: scalar branches below)
-        auto walk = [&](auto write_tag, auto exact_tag) {
+        auto walk = [&](auto write_tag, auto exact_tag, auto lj_tag) {
+            // (the second record: the LJ parameters, and its sign for the energy's weight and the prune's "j is mobile")
+            constexpr bool Q2 = ENERGY || decltype(write_tag)::value || decltype(lj_tag)::value;
+            const std::integral_constant<bool, Q2> rec_tag{};
 #pragma unroll
             for (int u0 = 0; u0 < NB_ATOM_U; u0 += NB_ATOM_G) {
                 if (u0 >= nch) break;   // wave-uniform (scalar branch)
                 if (u0 + NB_ATOM_G <= nch) {
                     u32x4 q4[NB_ATOM_G]; f32x2 q2[NB_ATOM_G];
 #pragma unroll
-                    for (int g = 0; g < NB_ATOM_G; g++) fetch(ent[u0 + g], q4[g], q2[g]);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 2 * NB_ATOM_G, 0);   // the DS reads first
+                    for (int g = 0; g < NB_ATOM_G; g++) fetch(ent[u0 + g], q4[g], q2[g], rec_tag);
+                    __builtin_amdgcn_sched_group_barrier(0x100, (Q2 ? 2 : 1) * NB_ATOM_G, 0);   // the DS reads first
 #pragma unroll
-                    for (int g = 0; g < NB_ATOM_G; g++) pair(ent[u0 + g], q4[g], q2[g], write_tag, exact_tag);
+                    for (int g = 0; g < NB_ATOM_G; g++) pair(ent[u0 + g], q4[g], q2[g], write_tag, exact_tag, lj_tag);
                 } else {
 #pragma unroll
                     for (int g = 0; g < NB_ATOM_G - 1; g++) {
                         if (u0 + g >= nch) break;
                         u32x4 q4; f32x2 q2;
-                        fetch(ent[u0 + g], q4, q2);
-                        pair(ent[u0 + g], q4, q2, write_tag, exact_tag);
+                        fetch(ent[u0 + g], q4, q2, rec_tag);
+                        pair(ent[u0 + g], q4, q2, write_tag, exact_tag, lj_tag);
                     }
                 }
             }
             for (int base = 64 * NB_ATOM_U; base < cnt; base += 64) {   // lists longer than the prefetch window (dense regions); padded like the others
                 const unsigned e = (unsigned)lst[base + lane];
                 u32x4 q4; f32x2 q2;
-                fetch(e, q4, q2);
-                pair(e, q4, q2, write_tag, exact_tag);
+                fetch(e, q4, q2, rec_tag);
+                pair(e, q4, q2, write_tag, exact_tag, lj_tag);
                 fx += (double)bx; fy += (double)by; fz += (double)bz; bx = by = bz = 0.0f;
             }
         };
-        if (!pruning) { if (exact) walk(std::false_type{}, std::true_type{}); else walk(std::false_type{}, std::false_type{}); }
-        else {
-            if (exact) walk(std::true_type{}, std::true_type{}); else walk(std::true_type{}, std::false_type{});
+        if (!pruning) {
+            if (exact) walk(std::false_type{}, std::true_type{}, std::true_type{});
+            else if (coul) { if constexpr (NB_COULOMB_WALK) walk(std::false_type{}, std::false_type{}, std::false_type{}); }
+            else walk(std::false_type{}, std::false_type{}, std::true_type{});
+        } else {
+            if (exact) walk(std::true_type{}, std::true_type{}, std::true_type{});
+            else if (coul) { if constexpr (NB_COULOMB_WALK) walk(std::true_type{}, std::false_type{}, std::false_type{}); }
+            else walk(std::true_type{}, std::false_type{}, std::true_type{});
             const int padto = min((pcnt + 63) & ~63, a.acap);
             if (pcnt + lane < padto) pout[pcnt + lane] = (unsigned short)ghost;   // whole chunks: the walk has no "lane holds an entry" mask
             if (lane == 0) {

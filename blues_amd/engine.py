@@ -67,6 +67,10 @@ class NativeEngine:
         spec = os.environ.get("BLUES_GROUP_LIST_SUPERSET")
         if spec:
             self._check(self._lib.blues_set_global(self._h, b"group_list_superset", float(int(spec))))
+        # development switch of the per-atom-list kernel's Coulomb-only walk for i-atoms without epsilon: 0 = every atom takes the full walk
+        spec = os.environ.get("BLUES_NB_COULOMB_WALK")
+        if spec:
+            self._check(self._lib.blues_set_global(self._h, b"nb_coulomb_walk", float(int(spec))))
         if system.positions is not None:
             self.set_positions(system.positions)
 
