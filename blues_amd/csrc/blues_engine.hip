@@ -371,6 +371,7 @@ struct BluesEngine {
     bool pme = false; int pme_K[3] = {0, 0, 0}, pme_order = 5, disp_corr = 0;
     std::vector<int> pme_frozen;   // NonbondedForce charges (alchemical atoms 0); frozen atoms that carry charge
     DBuf<double> d_qn, d_qn_full, d_frec, d_pme_e; DBuf<int> d_pme_frozen; DBuf<unsigned long long> d_pme_acc;
+    DBuf<int> d_pme_path;   // [2] mobile mesh launches served by the pruned in-LDS pipeline / by a general body, counted by the kernel (PmeArgs::path)
     PmeBufs<float> pme_f; PmeBufs<double> pme_d;
     bool pme_static_valid = false;
     // exact PME treatment of the alchemical charges (kernels_pme.h: k_pme_exact_b): the correction pairs, the per-slot force
@@ -2121,6 +2122,7 @@ template <typename T> static int pme_tables(BluesEngine* h) {
         P.eterm.upload(et);
         P.a_re.alloc(ng); P.a_im.alloc(ng); P.b_re.alloc(ng); P.b_im.alloc(ng); P.qf_re.alloc(ng); P.qf_im.alloc(ng); P.phi_f.alloc(ng);
         h->d_pme_acc.alloc(ng); h->d_pme_e.alloc(4); h->d_frec.alloc((size_t)3 * h->n);
+        if (!h->d_pme_path.p) h->d_pme_path.upload(std::vector<int>(2, 0));   // (the two counts live as long as the engine: a new box keeps them)
     } catch (std::string& e) { E_FAIL(h, "%s", e.c_str()); }
     // constants of the box: self term, neutralising background, dispersion correction
     double qsum = 0.0, q2 = 0.0;
@@ -2170,6 +2172,7 @@ template <typename T> static PmeArgs<T> make_pme_args(BluesEngine* h, bool is_st
     P.a_re = b.a_re.p; P.a_im = b.a_im.p; P.b_re = b.b_re.p; P.b_im = b.b_im.p; P.eterm = b.eterm.p;
     P.qf_re = b.qf_re.p; P.qf_im = b.qf_im.p; P.phi_f = b.phi_f.p; P.have_static = !h->pme_frozen.empty();
     P.frec = h->d_frec.p; P.epart = h->d_pme_e.p; P.want_energy = 0;
+    P.path = is_static ? nullptr : h->d_pme_path.p;
     return P;
 }
 
@@ -4502,6 +4505,11 @@ int blues_get_global(BluesEngine* h, const char* name, double* value) {
         if (h->d_sup_stat.p) HIP_OK(h, hipMemcpy(st, h->d_sup_stat.p, sizeof st, hipMemcpyDeviceToHost));   // (no layout has made room for supersets yet: 0, 0)
         *value = st[k == "group_list_superset_served" ? 0 : 1];
     }
+    else if (k == "pme_fast_launches" || k == "pme_general_launches") {   // (blues_get_pme_path, one word of it)
+        int64_t st[2];
+        if (blues_get_pme_path(h, st)) return 1;
+        *value = (double)st[k == "pme_fast_launches" ? 0 : 1];
+    }
     // i-slots of the current layout whose atom takes the per-atom-list kernel's Coulomb-only walk: those without epsilon (0 with the switch
     // off, with another nonbonded kernel, or where the kernel evaluates the erfc/exp form, which keeps the full walk)
     else if (k == "nb_coulomb_walk_atoms") *value = (h->nb_coulomb_walk && h->k1_mode == 2 && !h->ewpoly.exact) ? h->n_eps0_islots : 0;
@@ -4640,6 +4648,17 @@ int blues_get_cmap_angles(BluesEngine* h, double* out) {
     HIP_OK(h, hipGetLastError());
     HIP_OK(h, hipStreamSynchronize(h->stream));
     HIP_OK(h, hipMemcpy(out, h->d_cmap_angles.p, sizeof(double) * 2 * h->n_cmap, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int blues_get_pme_path(BluesEngine* h, int64_t out[2]) {
+    out[0] = out[1] = 0;
+    if (!h->pme || !h->d_pme_path.p) return 0;
+    int c[2];
+    hipSetDevice(h->device);
+    HIP_OK(h, hipStreamSynchronize(h->stream));   // (a batch member's launches ran on the batch's stream, which a batch call waits for before it returns)
+    HIP_OK(h, hipMemcpy(c, h->d_pme_path.p, sizeof c, hipMemcpyDeviceToHost));
+    out[0] = c[0]; out[1] = c[1];
     return 0;
 }
 

@@ -11,7 +11,7 @@
 // three axis transforms back -> gather) with workgroup barriers between the phases: no launch boundaries, the mesh stays
 // in the L2 of the replica's XCD.  Spreading accumulates in 64-bit fixed point (integer atomics commute: the result does
 // not depend on the order in which the atoms arrive, so a batched replica stays bitwise identical to a lone one).
-// The axis transforms are plain DFTs (K <= 64 per axis, any factorisation -- OpenMM's Reference platform takes the mesh
+// The axis transforms are plain DFTs (K <= 256 per axis, any factorisation -- OpenMM's Reference platform takes the mesh
 // sizes as ceil(...) gives them, 27 included).
 #pragma once
 #include "device_common.h"
@@ -37,6 +37,7 @@ template <typename T> struct PmeArgs {
     double* frec;                      // [3][n] force on the selected atoms
     double* epart;                     // [1] mesh energy 1/2 sum eterm |Q^_f + Q^_m|^2 (dynamic launch, when want_energy)
     int want_energy;
+    int* path;                         // [2] mobile launches served by the pruned in-LDS pipeline / by a general body (null: not counted -- the static launch)
 };
 
 template <typename T>
@@ -120,6 +121,7 @@ template <typename T, bool STATIC, int ORDER = 0>
 __device__ __forceinline__ void pme_body(const PmeArgs<T>& P) {
     const int tid = threadIdx.x, order = ORDER > 0 ? ORDER : P.order;
     const int K0 = P.K[0], K1 = P.K[1], K2 = P.K[2];
+    if (!STATIC && tid == 0 && P.path) P.path[1]++;   // (a general body served this mobile launch: the host's choice, or one of k_pme_fast's two exits)
     // ---- charge mesh in fixed point
     for (int g = tid; g < P.ng; g += PME_THREADS) P.acc[g] = 0ull;
     __syncthreads();
@@ -248,7 +250,9 @@ __device__ __forceinline__ void pme_pass(int in, int out, int nlines, int line_d
     // line l = (l / line_div, l % line_div); element j of its input sits at in_s0*(l/line_div) + in_s1*(l%line_div) + in_st*j and stands for
     // mesh index (k0 + j) mod K; output o stands for index (m0 + o) mod K.  A thread keeps ONE output index o and walks the lines
     // (its phase exp(DIR 2 pi i m k0 / K) and the per-input rotation are loop invariants; no integer division per work item).  The phase
-    // is advanced by a complex rotation per input (4 FMAs, no table look-up; <= 36 steps in fp32: ~2e-6 of a few % of the force).
+    // is advanced by a complex rotation per input (4 FMAs, no table look-up; <= 36 steps in fp32 on the benchmark mesh: ~2e-6 of a few % of
+    // the force; up to K = 256 steps on the longest axis the engine accepts -- measured on 6 x 8 x 256 and 256 x 6 x 8, the force is
+    // within 7.3e-7 of the oracle's, three times the general kernel's residual and 14 times inside the 1e-5 bound: profiles/pme_shapes/README.md).
     const int o = threadIdx.x % n_out, lg = threadIdx.x / n_out, nlg = PME_THREADS / n_out;
     if (lg >= nlg) return;   // (the threads past the last whole group of n_out sit this pass out)
     int m = m0 + o; if (m >= K) m -= K;
@@ -341,6 +345,7 @@ __device__ __forceinline__ void pme_fast_body(const PmeArgs<float>& P) {
     fits = Lx * Ly * Lz <= PME_LDS_X && Lx * K1 * Hz <= PME_LDS_X && Lx * Ly * Hz <= PME_LDS_Y && K0 * K1 * Hz <= PME_LDS_Y
            && P.n_sel * 16 <= PME_LDS_X && (Lx * Ly * Lz + 4 + P.n_sel * 48 + 1) / 2 <= PME_LDS_Y;   // (room for the atoms' spline weights beside the meshes)
     if (!fits) { pme_body_general_f(P); return; }   // (block-uniform) a spread-out mobile set: the general path
+    if (tid == 0 && P.path) P.path[0]++;   // (read by blues_get_global "pme_fast_launches": the pruned pipeline served this launch)
     // ---- spread into the block (LDS, 64-bit integer adds: order-independent)
     for (int g = tid; g < Lx * Ly * Lz; g += PME_THREADS) acc[g] = 0;
     __syncthreads();

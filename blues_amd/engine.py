@@ -223,7 +223,11 @@ class NativeEngine:
         path = (C.c_int64 * 2)()   # (exact PME treatment: launches of its mesh kernel by path; a library without the entry has no such engines)
         if hasattr(self._lib, "blues_get_exact_pme_path"):
             self._check(self._lib.blues_get_exact_pme_path(self._h, path))
-        return {"exact_pme_fast_launches": int(path[0]), "exact_pme_general_launches": int(path[1]),
+        plain = (C.c_int64 * 2)()   # (plain mesh kernel: mobile launches served by the pruned in-LDS pipeline / by a general body, counted on the device)
+        if hasattr(self._lib, "blues_get_pme_path"):
+            self._check(self._lib.blues_get_pme_path(self._h, plain))
+        return {"pme_fast_launches": int(plain[0]), "pme_general_launches": int(plain[1]),
+                "exact_pme_fast_launches": int(path[0]), "exact_pme_general_launches": int(path[1]),
                 "force_passes": s[0], "list_generation": s[1], "kernel_launches": s[2], "i_tiles": s[3],
                 "clusters": s[4], "jcap": s[5], "npart": s[6], "seg_len": s[7] // 1000, "wpb": s[7] % 1000,
                 "max_jcount": s[8], "resorts": s[9], "list_builds": s[10], "own_energy_evaluations": s[11],

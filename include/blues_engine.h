@@ -408,6 +408,11 @@ int blues_get_stats(BluesEngine *h, int64_t stats[BLUES_N_STATS]);
  * served them: [0] the pruned in-LDS pipeline (mixed precision, mesh and atoms fit), [1] the general one.  Zeros for any other engine.
  * Additive (BLUES_ABI_VERSION unchanged). */
 int blues_get_exact_pme_path(BluesEngine *h, int64_t out[2]);
+/* nonbonded_method PME: mobile launches of the reciprocal-space kernel so far, counted on the device by the body that served them:
+ * [0] the pruned in-LDS pipeline, [1] a general body (the host's choice of kernel, or one of the pruned kernel's two in-kernel exits).
+ * The static launch of the frozen charges is not counted.  Zeros without reciprocal space.  blues_get_global("pme_fast_launches") and
+ * ("pme_general_launches") give one word each.  Additive (BLUES_ABI_VERSION unchanged). */
+int blues_get_pme_path(BluesEngine *h, int64_t out[2]);
 /* time `reps` launches of the dominant nonbonded kernel alone with HIP events
  * on the engine's own stream; returns mean microseconds per launch. */
 int blues_time_nonbonded(BluesEngine *h, int32_t reps, double *usec_per_launch);

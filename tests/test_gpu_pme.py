@@ -43,6 +43,8 @@ def test_energy_and_forces_with_reciprocal_space(Engine, oracle_mod, tol_box, pr
         assert abs(tg.sum() - eo) <= tol * abs(eo)
         assert g.potential_energy() == pytest.approx(tg.sum(), rel=1e-14)
         assert _rel(g.get_forces(), fo) <= tol
+    st = g.stats()      # 975 mobile atoms: more than k_pme_fast caches -- its in-kernel exit to the general body; double precision never starts it
+    assert st["pme_fast_launches"] == 0 and st["pme_general_launches"] > 0
     g.close()
 
 
@@ -65,6 +67,8 @@ def test_s23k_frozen_environment_static_and_mobile_meshes(Engine, oracle_mod, pr
         x = o.get_positions(); rng = np.random.RandomState(3)
         x[mob] += rng.normal(scale=0.004, size=(int(mob.sum()), 3))          # (constraints are not enforced by an evaluation)
         g.set_positions(x); o.set_positions(x)
+    st = g.stats()      # mixed precision on 18 x 27 x 36 with 275 mobile atoms: the pruned in-LDS pipeline, every launch
+    assert (st["pme_fast_launches"] > 0 and st["pme_general_launches"] == 0) if precision == 0 else (st["pme_fast_launches"] == 0 and st["pme_general_launches"] > 0)
     g.close()
 
 
@@ -83,6 +87,8 @@ def test_switch_with_reciprocal_space(Engine, oracle_mod, tol_box, precision, to
     wo = np.array(wo)
     assert np.abs(wg - wo).max() <= tol * np.abs(wo).max()
     assert np.abs(g.get_positions() - o.get_positions()).max() < (1e-9 if precision else 2e-4)
+    st = g.stats()      # (all-mobile box: every launch of the switch through a general body)
+    assert st["pme_fast_launches"] == 0 and st["pme_general_launches"] >= n
     # the trajectory is not the direct-space one (the forces on the water differ), the work of the first lambda step is (same x0)
     od = oracle_mod.Oracle(s, data); od.set_velocities(v); od.step(n)
     assert abs(od.get_global("protocol_work") - wo[-1]) > 1e-4
