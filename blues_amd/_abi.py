@@ -84,7 +84,15 @@ class BluesSystemExt(C.Structure):
                 ("n_cmap_torsions", C.c_int32), ("cmap_torsion_map", _ip), ("cmap_torsion_atoms", _ip)]
 
 
+class BluesSystemExtV3(C.Structure):
+    """include/blues_engine.h: BluesSystemExtV3 (BluesSystemExt grown at its end by the CHARMM terms; passed to blues_engine_create_ext
+    in BluesSystemExt's place with struct_size = its own size)."""
+    _fields_ = BluesSystemExt._fields_ + [("n_urey_bradley", C.c_int32), ("urey_bradley_atoms", _ip), ("urey_bradley_params", _dp),
+                                          ("n_impropers", C.c_int32), ("improper_atoms", _ip), ("improper_params", _dp)]
+
+
 SYSTEM_EXT_SIZE_V1 = 8                     # a caller from before the CMAP fields: struct_size, alchemical_pme_treatment
+SYSTEM_EXT_SIZE_V2 = C.sizeof(BluesSystemExt)   # BLUES_SYSTEM_EXT_SIZE_V2: a caller with maps but no Urey-Bradley terms or impropers
 CMAP_MIN_SIZE, CMAP_MAX_SIZE = 4, 64       # BLUES_CMAP_MIN_SIZE / BLUES_CMAP_MAX_SIZE
 
 
@@ -227,6 +235,12 @@ class SystemData:
     alchemical_pme_treatment: str = "direct-space"   # NB_PME: "direct-space" or "exact" (openmmtools' alchemical_pme_treatment; blues_engine_create_ext)
     cmap_maps: tuple = ()                # CMAPTorsionForce maps: (n, n) arrays, kJ/mol, E[i, j] at phi = 2 pi i / n, psi = 2 pi j / n (blues_engine_create_ext)
     cmap_torsions: np.ndarray = field(default_factory=lambda: np.zeros((0, 9), np.int32))   # (m, 9): map, a1..a4 (phi), b1..b4 (psi)
+    # CHARMM terms of a chamber topology (blues_engine_create_ext).  Urey-Bradley: E = 0.5 k (r - r0)^2 between the 1-3 atoms of an
+    # angle -- a force, not a bond: it joins no molecule, fragment or constraint.  Improper: E = k (psi - psi0)^2, psi the dihedral 1-2-3-4
+    urey_bradley_atoms: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.int32))
+    urey_bradley_params: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))   # (n, 2): r0 nm, k kJ/mol/nm^2
+    improper_atoms: np.ndarray = field(default_factory=lambda: np.zeros((0, 4), np.int32))
+    improper_params: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))       # (n, 2): psi0 rad, k kJ/mol/rad^2
 
     def __post_init__(self):
         alchemical_pme_treatment_code(self.alchemical_pme_treatment)
@@ -257,14 +271,19 @@ class SystemData:
     def has_cmap(self):
         return len(tuple(self.cmap_maps or ())) > 0 or np.asarray(self.cmap_torsions).size > 0
 
+    @property
+    def has_charmm(self):
+        return np.asarray(self.urey_bradley_atoms).size > 0 or np.asarray(self.improper_atoms).size > 0
+
     def ext_desc(self):
-        """BluesSystemExt of this System, or None where blues_engine_create / blues_engine_create_gb say everything.  The numpy
-        buffers of the maps stay alive with the descriptor (its _keep)."""
+        """BluesSystemExt of this System -- BluesSystemExtV3 where it carries Urey-Bradley terms or impropers --, or None where
+        blues_engine_create / blues_engine_create_gb say everything.  The numpy buffers of the maps and of the CHARMM terms stay alive
+        with the descriptor (its _keep)."""
         code = alchemical_pme_treatment_code(self.alchemical_pme_treatment)
-        if code == 0 and not self.has_cmap:
+        if code == 0 and not self.has_cmap and not self.has_charmm:
             return None
-        d = BluesSystemExt()
-        d.struct_size = C.sizeof(BluesSystemExt); d.alchemical_pme_treatment = code
+        d = BluesSystemExtV3() if self.has_charmm else BluesSystemExt()
+        d.struct_size = C.sizeof(d); d.alchemical_pme_treatment = code
         if self.has_cmap:
             maps = [_f64(m) for m in self.cmap_maps]
             tors = _i32(self.cmap_torsions, (-1, 9))
@@ -276,7 +295,37 @@ class SystemData:
             d.cmap_size = keep["size"].ctypes.data_as(_ip); d.cmap_energy = keep["energy"].ctypes.data_as(_dp)
             d.cmap_torsion_map = keep["map"].ctypes.data_as(_ip); d.cmap_torsion_atoms = keep["atoms"].ctypes.data_as(_ip)
             d._keep = keep
+        if self.has_charmm:
+            keep = getattr(d, "_keep", {})
+            keep.update({"ub_atoms": _i32(self.urey_bradley_atoms, (-1, 2)), "ub_params": _f64(self.urey_bradley_params, (-1, 2)),
+                         "impr_atoms": _i32(self.improper_atoms, (-1, 4)), "impr_params": _f64(self.improper_params, (-1, 2))})
+            d.n_urey_bradley = len(keep["ub_atoms"]); d.n_impropers = len(keep["impr_atoms"])
+            d.urey_bradley_atoms = keep["ub_atoms"].ctypes.data_as(_ip); d.urey_bradley_params = keep["ub_params"].ctypes.data_as(_dp)
+            d.improper_atoms = keep["impr_atoms"].ctypes.data_as(_ip); d.improper_params = keep["impr_params"].ctypes.data_as(_dp)
+            d._keep = keep
         return d
+
+    def check_charmm(self):
+        """What blues_engine_create_ext refuses about the Urey-Bradley terms and the impropers, raised before a library is loaded
+        (ValueError)."""
+        for label, atoms, params, width in (("Urey-Bradley term", self.urey_bradley_atoms, self.urey_bradley_params, 2),
+                                            ("improper", self.improper_atoms, self.improper_params, 4)):
+            atoms, params = np.asarray(atoms), np.asarray(params, dtype=np.float64)
+            if atoms.size == 0 and params.size == 0:
+                continue
+            if atoms.ndim != 2 or atoms.shape[1] != width or params.ndim != 2 or params.shape != (len(atoms), 2):
+                raise ValueError("%ss: an (n, %d) array of atoms and an (n, 2) array of parameters; got shapes %s and %s" % (label, width, atoms.shape, params.shape))
+            for t, (row, (x0, k)) in enumerate(zip(atoms, params)):
+                if np.any(row < 0) or np.any(row >= self.n_atoms):
+                    raise ValueError("%s %d: atom index out of range" % (label, t))
+                if len(set(int(a) for a in row)) != width:
+                    raise ValueError("%s %d: two equal atoms within one term" % (label, t))
+                if not np.isfinite(k) or k < 0.0:
+                    raise ValueError("%s %d: force constant %g is negative or not finite" % (label, t, k))
+                if width == 2 and not (np.isfinite(x0) and x0 > 0.0):
+                    raise ValueError("%s %d: r0 %g is not a positive length" % (label, t, x0))
+                if width == 4 and not abs(x0) <= np.pi:
+                    raise ValueError("%s %d: psi0 %g lies outside [-pi, pi]" % (label, t, x0))
 
     def check_cmap(self):
         """What blues_engine_create_ext refuses about the CMAP maps and torsions, raised before a library is loaded (ValueError)."""
@@ -473,7 +522,7 @@ def declare_engine_prototypes(lib):
     protos = {
         "blues_engine_create": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.c_int, C.POINTER(H)], C.c_int),
         "blues_engine_create_gb": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_int, C.POINTER(H)], C.c_int),
-        "blues_engine_create_ext": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.POINTER(BluesSystemExt), C.c_int, C.POINTER(H)], C.c_int),
+        "blues_engine_create_ext": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_void_p, C.c_int, C.POINTER(H)], C.c_int),   # (ext: BluesSystemExt or BluesSystemExtV3, told apart by struct_size)
         "blues_engine_destroy": ([H], C.c_int),
         "blues_last_error": ([H], C.c_char_p),
         "blues_abi_version": ([], C.c_int),

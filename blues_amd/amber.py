@@ -21,10 +21,19 @@ WATER_NAMES = ("WAT", "HOH", "TIP3", "TP3", "SPC")
 
 
 def _parse_format(fmt):
+    """Fortran format of a prmtop section -> (repeat count, kind, field width).  Besides the counted descriptors of an Amber file
+    ((10I8), (5E16.8), (20a4)) chamber writes one without a count -- (a80), under CTITLE: count 1 -- and a mixed one -- (i2,a78), under
+    FORCE_FIELD_TYPE: kind "line", width 0, the section's lines are kept as they stand."""
     m = re.match(r"\(?(\d+)([aAiIeEfF])(\d+)(?:\.(\d+))?\)?", fmt.strip())
-    if not m:
-        raise ValueError("unsupported prmtop format %r" % fmt)
-    return int(m.group(1)), m.group(2).lower(), int(m.group(3))
+    if m:
+        return int(m.group(1)), m.group(2).lower(), int(m.group(3))
+    one = r"\d*[aAiIeEfF]\d+(?:\.\d+)?"
+    m = re.fullmatch(r"\(([aAiIeEfF])(\d+)(?:\.(\d+))?\)", fmt.strip())
+    if m:
+        return 1, m.group(1).lower(), int(m.group(2))
+    if re.fullmatch(r"\(%s(?:,%s)+\)" % (one, one), fmt.strip().replace(" ", "")):
+        return 1, "line", 0
+    raise ValueError("unsupported prmtop format %r" % fmt)
 
 
 def read_prmtop(path):
@@ -36,6 +45,9 @@ def read_prmtop(path):
         if name is None:
             return
         _, kind, width = fmt
+        if kind == "line":   # (a mixed descriptor: the lines as strings)
+            flags[name] = [line.rstrip("\n") for line in buf]
+            return
         items = []
         for line in buf:
             line = line.rstrip("\n")
@@ -175,6 +187,93 @@ def cmap_from_prmtop(prm, natom=None):
     return tuple(maps), tors
 
 
+def is_chamber(prm):
+    """A topology written by chamber (CHARMM force field in prmtop form): it carries FORCE_FIELD_TYPE, CTITLE or a CHARMM_* section."""
+    return "FORCE_FIELD_TYPE" in prm or "CTITLE" in prm or any(str(k).startswith("CHARMM_") for k in prm)
+
+
+def charmm_from_prmtop(prm, natom=None):
+    """The Urey-Bradley and improper sections of a chamber prmtop -> (urey_bradley_atoms, urey_bradley_params, improper_atoms,
+    improper_params) as SystemData holds them; four empty arrays without them.
+
+    The layout is recalled from ParmEd, not source-pinned (DESIGN.md 4m): CHARMM_UREY_BRADLEY_COUNT = (terms, types);
+    CHARMM_UREY_BRADLEY holds three integers per term, two 1-based ATOM NUMBERS (not the coordinate offsets of BONDS_*) and a 1-based
+    type; CHARMM_UREY_BRADLEY_FORCE_CONSTANT in kcal/mol/A^2 and _EQUIL_VALUE in A.  CHARMM writes K (S - S0)^2, stored here as OpenMM's
+    0.5 k (r - r0)^2: r0 = 0.1 S0, k = 2 K 4.184 100.  CHARMM_NUM_IMPROPERS, CHARMM_NUM_IMPR_TYPES; CHARMM_IMPROPERS holds five integers
+    per term, four 1-based atom numbers and a 1-based type; CHARMM_IMPROPER_FORCE_CONSTANT in kcal/mol/rad^2 and _PHASE in degrees:
+    E = k (psi - psi0)^2 with k = 4.184 K, psi0 in radians.  ValueError, with the reason, for counts that do not match the sections,
+    a type or atom out of range and two equal atoms within one term."""
+    def ints(name):
+        return np.asarray(prm.get(name, ()), dtype=np.int64).reshape(-1)
+
+    def floats(name):
+        return np.asarray(prm.get(name, ()), dtype=np.float64).reshape(-1)
+
+    def section(label, index_name, width, nterm, ntype, const_names):
+        consts = [floats(c) for c in const_names]
+        for c, name in zip(consts, const_names):
+            if len(c) != ntype:
+                raise ValueError("%s: %d types are announced but %s holds %d values" % (label, ntype, name, len(c)))
+        index = ints(index_name)
+        if len(index) != (width + 1) * nterm:
+            raise ValueError("%s: %d terms are announced but %s holds %d integers (%d per term)" % (label, nterm, index_name, len(index), width + 1))
+        index = index.reshape(-1, width + 1)
+        for t, row in enumerate(index):
+            if row[width] < 1 or row[width] > ntype:
+                raise ValueError("%s %d: type %d of %d" % (label, t + 1, row[width], ntype))
+            a = row[:width] - 1
+            if np.any(a < 0) or (natom is not None and np.any(a >= natom)):
+                raise ValueError("%s %d: atom out of range" % (label, t + 1))
+            if len(set(int(v) for v in a)) != width:
+                raise ValueError("%s %d: two equal atoms within one term" % (label, t + 1))
+        return (index[:, :width] - 1).astype(np.int32), index[:, width] - 1, consts
+
+    ub_atoms, ub_params = np.zeros((0, 2), np.int32), np.zeros((0, 2))
+    if "CHARMM_UREY_BRADLEY_COUNT" in prm or "CHARMM_UREY_BRADLEY" in prm:
+        count = ints("CHARMM_UREY_BRADLEY_COUNT")
+        if len(count) != 2:
+            raise ValueError("CHARMM_UREY_BRADLEY_COUNT holds %d values, not (terms, types)" % len(count))
+        ub_atoms, ty, (kk, s0) = section("Urey-Bradley term", "CHARMM_UREY_BRADLEY", 2, int(count[0]), int(count[1]),
+                                         ("CHARMM_UREY_BRADLEY_FORCE_CONSTANT", "CHARMM_UREY_BRADLEY_EQUIL_VALUE"))
+        ub_params = np.stack([0.1 * s0[ty], 2.0 * kk[ty] * KCAL * 100.0], axis=1).reshape(-1, 2)
+    im_atoms, im_params = np.zeros((0, 4), np.int32), np.zeros((0, 2))
+    if "CHARMM_NUM_IMPROPERS" in prm or "CHARMM_IMPROPERS" in prm:
+        nterm, ntype = ints("CHARMM_NUM_IMPROPERS"), ints("CHARMM_NUM_IMPR_TYPES")
+        if len(nterm) != 1 or len(ntype) != 1:
+            raise ValueError("CHARMM_NUM_IMPROPERS / CHARMM_NUM_IMPR_TYPES hold %d and %d values, not one each" % (len(nterm), len(ntype)))
+        im_atoms, ty, (kk, ph) = section("improper", "CHARMM_IMPROPERS", 4, int(nterm[0]), int(ntype[0]),
+                                         ("CHARMM_IMPROPER_FORCE_CONSTANT", "CHARMM_IMPROPER_PHASE"))
+        im_params = np.stack([np.deg2rad(ph[ty]), KCAL * kk[ty]], axis=1).reshape(-1, 2)
+    return ub_atoms.reshape(-1, 2), ub_params, im_atoms.reshape(-1, 4), im_params
+
+
+def _refuse_nbfix(prm, ntypes):
+    """ValueError naming the type pair whose off-diagonal entry of the main Lennard-Jones table is not the Lorentz-Berthelot combination
+    of the diagonal ones (Rmin arithmetic mean, eps geometric mean) to 1e-6 relative: a CHARMM NBFIX, which per-atom sigma / epsilon
+    cannot represent.  (The table is written with eight significant digits.)"""
+    nbidx, acoef, bcoef = prm["NONBONDED_PARM_INDEX"], prm["LENNARD_JONES_ACOEF"], prm["LENNARD_JONES_BCOEF"]
+    rmin, eps = np.zeros(ntypes), np.zeros(ntypes)
+    for t in range(ntypes):
+        k = int(nbidx[ntypes * t + t]) - 1
+        if k >= 0 and acoef[k] != 0.0 and bcoef[k] != 0.0:
+            rmin[t], eps[t] = (2.0 * acoef[k] / bcoef[k]) ** (1.0 / 6.0), bcoef[k] ** 2 / (4.0 * acoef[k])
+    names = {}
+    for i, t in enumerate(np.asarray(prm.get("ATOM_TYPE_INDEX", ()))):
+        if "AMBER_ATOM_TYPE" in prm and int(t) - 1 not in names:
+            names[int(t) - 1] = prm["AMBER_ATOM_TYPE"][i]
+    for a in range(ntypes):
+        for b in range(a + 1, ntypes):
+            k = int(nbidx[ntypes * a + b]) - 1
+            if k < 0:
+                continue
+            e, r6 = np.sqrt(eps[a] * eps[b]), (0.5 * (rmin[a] + rmin[b])) ** 6
+            for got, want, which in ((acoef[k], e * r6 * r6, "ACOEF"), (bcoef[k], 2.0 * e * r6, "BCOEF")):
+                if abs(got - want) > 1e-6 * max(abs(got), abs(want)):
+                    raise ValueError("NBFIX: LENNARD_JONES_%s of the type pair (%d, %d)%s is %.8e, the Lorentz-Berthelot combination of the "
+                                     "types' own entries gives %.8e; per-atom sigma / epsilon cannot represent a pair-specific entry"
+                                     % (which, a + 1, b + 1, " [%s, %s]" % (names[a], names[b]) if a in names and b in names else "", got, want))
+
+
 def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.005, constraints="HBonds",
                       rigid_water=True, hydrogen_mass=None, remove_cm_motion=True, alchemical_atoms=(),
                       tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME",
@@ -232,6 +331,14 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     tidx = prm["ATOM_TYPE_INDEX"]
     nbidx = prm["NONBONDED_PARM_INDEX"]
     acoef, bcoef = prm["LENNARD_JONES_ACOEF"], prm["LENNARD_JONES_BCOEF"]
+    chamber = is_chamber(prm)
+    if chamber:   # (1-4 pairs from the topology's own table; a non-chamber prmtop takes the path it always took)
+        _refuse_nbfix(prm, ntypes)
+    table14 = chamber and "LENNARD_JONES_14_ACOEF" in prm and "LENNARD_JONES_14_BCOEF" in prm   # (without the table: the diagonal entries, as for Amber)
+    if table14:
+        acoef14, bcoef14 = prm["LENNARD_JONES_14_ACOEF"], prm["LENNARD_JONES_14_BCOEF"]
+        if len(acoef14) != len(acoef) or len(bcoef14) != len(bcoef):
+            raise ValueError("LENNARD_JONES_14_ACOEF / _BCOEF hold %d and %d values, the main table %d" % (len(acoef14), len(bcoef14), len(acoef)))
     res_ptr = list(prm["RESIDUE_POINTER"] - 1) + [natom]
     res_lab = prm["RESIDUE_LABEL"]
     residue_of_atom = np.zeros(natom, dtype=np.int32)
@@ -278,8 +385,8 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     bk, br = prm["BOND_FORCE_CONSTANT"], prm["BOND_EQUIL_VALUE"]
     ak, at = prm["ANGLE_FORCE_CONSTANT"], prm["ANGLE_EQUIL_VALUE"]
     dk, dn, dp = prm["DIHEDRAL_FORCE_CONSTANT"], prm["DIHEDRAL_PERIODICITY"], prm["DIHEDRAL_PHASE"]
-    scee = prm.get("SCEE_SCALE_FACTOR", np.full(len(dk), 1.2))
-    scnb = prm.get("SCNB_SCALE_FACTOR", np.full(len(dk), 2.0))
+    scee = prm.get("SCEE_SCALE_FACTOR", np.full(len(dk), 1.0 if table14 else 1.2))
+    scnb = prm.get("SCNB_SCALE_FACTOR", np.full(len(dk), 1.0 if table14 else 2.0))
 
     # hydrogen mass repartitioning (createSystem(hydrogenMass=...))
     if hydrogen_mass is not None:
@@ -336,7 +443,18 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
             tors_atoms.append((i, j, k_, l)); tors_params.append((round(abs(dn[t])), dp[t], dk[t] * KCAL))
         if int(d[2]) >= 0 and int(d[3]) >= 0:  # carries a 1-4 interaction
             pair = (min(i, l), max(i, l))
-            if pair not in exc:
+            if pair not in exc and table14:   # CHARMM's own 1-4 table, indexed like the main one
+                ti, tl = int(tidx[i]), int(tidx[l])
+                if ti <= 0 or tl <= 0:
+                    raise ValueError("1-4 pair (%d, %d): an atom without a Lennard-Jones type" % (i, l))
+                k14 = int(nbidx[ntypes * (ti - 1) + (tl - 1)]) - 1
+                a14, b14 = (acoef14[k14], bcoef14[k14]) if k14 >= 0 else (0.0, 0.0)
+                qq = charge[i] * charge[l] / (scee[t] if scee[t] != 0 else 1.0)
+                if a14 == 0.0 or b14 == 0.0:
+                    exc[pair] = (qq, 0.1, 0.0)
+                else:
+                    exc[pair] = (qq, 0.1 * (a14 / b14) ** (1.0 / 6.0), KCAL * b14 * b14 / (4.0 * a14) / (scnb[t] if scnb[t] != 0 else 1.0))
+            elif pair not in exc:
                 qq = charge[i] * charge[l] / (scee[t] if scee[t] != 0 else 1.2)
                 e14 = np.sqrt(eps[i] * eps[l]) / (scnb[t] if scnb[t] != 0 else 2.0)
                 exc[pair] = (qq, 0.5 * (sigma[i] + sigma[l]), e14)
@@ -383,6 +501,9 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     )
     system.cmap_maps, system.cmap_torsions = cmap_from_prmtop(prm, natom)   # (CMAPTorsionForce of ff19SB / chamber topologies)
     system.check_cmap()
+    if chamber:   # (HarmonicBondForce of the Urey-Bradley terms, CustomTorsionForce of the impropers)
+        system.urey_bradley_atoms, system.urey_bradley_params, system.improper_atoms, system.improper_params = charmm_from_prmtop(prm, natom)
+    system.check_charmm()
     system.check_implicit_solvent()
     system.check_alchemical_pme_treatment()
     return system

@@ -45,6 +45,12 @@
 static_assert(CENT_GROUP == BLUES_MAX_CENTROID_GROUP, "a centroid-bond term has one place per atom the C-ABI allows in a group (kernels_bonded.h, build_bonded)");
 static_assert(T_CENT >= T_NTYPES, "T_CENT is an entry type only: it has no slot in the per-type arrays");
 static_assert(T_CMAP > T_CENT, "T_CMAP is an entry type only, past T_CENT");
+static_assert(T_UREY > T_CMAP && T_IMPR > T_UREY, "T_UREY and T_IMPR are entry types only, past T_CMAP");
+static_assert(sizeof(BluesSystemExt) == BLUES_SYSTEM_EXT_SIZE_V2 && offsetof(BluesSystemExtV3, n_urey_bradley) == BLUES_SYSTEM_EXT_SIZE_V2, "the CHARMM fields begin where BluesSystemExt ends");
+// BluesSystemExtV3 begins with BluesSystemExt's layout, field for field: the two cannot drift apart
+#define BLUES_EXT_SAME(f) static_assert(offsetof(BluesSystemExtV3, f) == offsetof(BluesSystemExt, f) && sizeof(((BluesSystemExtV3*)nullptr)->f) == sizeof(((BluesSystemExt*)nullptr)->f), "BluesSystemExtV3." #f " lies where BluesSystemExt has it")
+BLUES_EXT_SAME(struct_size); BLUES_EXT_SAME(alchemical_pme_treatment); BLUES_EXT_SAME(n_cmap_maps); BLUES_EXT_SAME(cmap_size); BLUES_EXT_SAME(cmap_energy); BLUES_EXT_SAME(n_cmap_torsions); BLUES_EXT_SAME(cmap_torsion_map); BLUES_EXT_SAME(cmap_torsion_atoms);
+#undef BLUES_EXT_SAME
 
 static thread_local std::string g_create_error;
 // set-up cost accounting (diagnostic, blues_debug_setup_seconds): [0] blues_engine_create, [1] sort_and_tile, [2] its device uploads,
@@ -212,6 +218,10 @@ struct HostTopology {
     std::vector<int32_t> cmap_size, cmap_tor_map, cmap_tor_atoms, cmap_first;
     std::vector<double> cmap_energy, cmap_coef;
     std::mutex cmap_mu; std::map<int, std::shared_ptr<DBuf<double>>> cmap_dev;
+    // CHARMM's Urey-Bradley terms and harmonic impropers (BluesSystemExt) as the caller gave them.  The Urey-Bradley pairs are NOT in
+    // link_pairs: they are forces between 1-3 atoms and hold no molecule together
+    std::vector<int32_t> ub_atoms, impr_atoms;
+    std::vector<double> ub_params, impr_params;
 };
 
 struct BluesEngine {
@@ -387,6 +397,8 @@ struct BluesEngine {
     int n_terms[T_NTYPES] = {0, 0, 0, 0, 0, 0}; int n_rows = 0; double restr_k = 0;
     int n_cent = 0; DBuf<int> d_cent_atoms; DBuf<double> d_cent_params;   // harmonic centroid bonds (kernels_bonded.h: T_CENT, the CENT = true kernels)
     int n_cmap = 0; DBuf<int> d_cmap_atoms, d_cmap_grid; std::shared_ptr<DBuf<double>> d_cmap_coef; DBuf<double> d_cmap_angles;   // CMAP torsions (T_CMAP, the CMAP = true kernels)
+    int n_ub = 0, n_impr = 0; DBuf<int> d_ub_atoms, d_impr_atoms; DBuf<double> d_ub_params, d_impr_params;   // Urey-Bradley terms and impropers (T_UREY, T_IMPR: they ride with the CMAP = true kernels)
+    bool entry_only_terms() const { return n_cmap > 0 || n_ub > 0 || n_impr > 0; }   // what the CMAP = true instantiations are launched for
     // pending integrate program
     Program prog; unsigned prog_draw_base = 0; int prog_trace = -1; bool tracing = false;
     // stats
@@ -922,6 +934,15 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
         if (!dev) { dev = std::make_shared<DBuf<double>>(); dev->upload(h->T->cmap_coef); }
         h->d_cmap_coef = dev;
     }
+    // Urey-Bradley terms and impropers (validated by create_impl): every mobile atom of a term owns one entry, role = its place in
+    // the term; all atoms frozen: energy only
+    h->n_ub = (int)(h->T->ub_atoms.size() / 2); h->n_impr = (int)(h->T->impr_atoms.size() / 4);
+    for (int t = 0; t < h->n_ub; t++)
+        for (int r = 0; r < 2; r++) { const int a = h->T->ub_atoms[2 * (size_t)t + r]; if (h->T->mass[a] != 0.0) { rtype[a].push_back(T_UREY); rterm[a].push_back(t); rrole[a].push_back(r); } }
+    for (int t = 0; t < h->n_impr; t++)
+        for (int r = 0; r < 4; r++) { const int a = h->T->impr_atoms[4 * (size_t)t + r]; if (h->T->mass[a] != 0.0) { rtype[a].push_back(T_IMPR); rterm[a].push_back(t); rrole[a].push_back(r); } }
+    if (h->n_ub > 0) { h->d_ub_atoms.upload(std::vector<int>(h->T->ub_atoms.begin(), h->T->ub_atoms.end())); h->d_ub_params.upload(h->T->ub_params); }
+    if (h->n_impr > 0) { h->d_impr_atoms.upload(std::vector<int>(h->T->impr_atoms.begin(), h->T->impr_atoms.end())); h->d_impr_params.upload(h->T->impr_params); }
     std::vector<int> row_atom, row_start(1, 0), et, ei, er;
     for (int i = 0; i < h->n; i++) if (!rtype[i].empty()) {
         row_atom.push_back(i);
@@ -932,7 +953,7 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
     { std::vector<int> row_of(h->n, -1); for (int r = 0; r < h->n_rows; r++) row_of[row_atom[r]] = r; h->d_row_of_orig.upload(row_of); h->h_row_of_orig = row_of; h->h_row_start = row_start; }
     h->d_fent.alloc((size_t)3 * std::max(1, h->n_entries));
     h->d_row_atom.upload(row_atom); h->d_row_start.upload(row_start); h->d_ent_type.upload(et); h->d_ent_term.upload(ei); h->d_ent_role.upload(er);
-    int total_terms = h->n_cent + h->n_cmap; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
+    int total_terms = h->n_cent + h->n_cmap + h->n_ub + h->n_impr; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     h->d_epart_b.alloc((size_t)((total_terms + 255) / 256 + 1) * T_NTYPES);
     // alchemical exception rows
     std::vector<int> es(1, 0), ep, eo; std::vector<double> epar;
@@ -1151,7 +1172,7 @@ static int sort_and_tile(BluesEngine* h) {
         h->fuse_forces = nit * h->batch_R <= 32;
         if (h->tune.fuse_forces >= 0) h->fuse_forces = h->tune.fuse_forces != 0;
         if (h->n_gen()) h->fuse_forces = false;   // (general constraint clusters: the decomposed force pass and k_finalize only)
-        if (h->n_cmap > 0) h->fuse_forces = false;   // (CMAP torsions: the fused force launch runs the plain bonded body, which does not know the entry type)
+        if (h->entry_only_terms()) h->fuse_forces = false;   // (CMAP torsions, Urey-Bradley terms, impropers: the fused force launch runs the plain bonded body, which does not know the entry types)
         if (h->fuse_forces) { WPB = 4; NW = std::max(4, NW / 3); }  // ~3 segments per wave: as long as the alchemical role
         NW = std::max(WPB, (NW / WPB) * WPB);
         if (h->pin_jcap > 0 && h->batch && std::min<double>(n, est / 1.8 * 1.2) + 64 <= h->pin_jcap) { jcap = h->pin_jcap; h->jcap = jcap; CH = h->pin_seg; NW = h->pin_nw; WPB = h->pin_wpb; }
@@ -1972,6 +1993,7 @@ static BondedArgs make_bonded_args(BluesEngine* h) {
     B.n_mobile = (int)h->mobile.size(); B.n_noise = h->n_noise; B.mobile_atoms = h->d_mobile_atoms.p; B.noise = h->d_noise.p;
     B.n_cent = h->n_cent; B.cent_atoms = h->d_cent_atoms.p; B.cent_params = h->d_cent_params.p;
     B.n_cmap = h->n_cmap; B.cmap_atoms = h->d_cmap_atoms.p; B.cmap_grid = h->d_cmap_grid.p; B.cmap_coef = h->d_cmap_coef ? h->d_cmap_coef->p : nullptr;
+    B.n_ub = h->n_ub; B.ub_atoms = h->d_ub_atoms.p; B.ub_params = h->d_ub_params.p; B.n_impr = h->n_impr; B.impr_atoms = h->d_impr_atoms.p; B.impr_params = h->d_impr_params.p;
     B.seed = h->seed; B.stream = (unsigned)h->replica * 4u; B.draw_base = h->h_draw; B.n_entry_blocks = (h->n_entries + 127) / 128;
     return B;
 }
@@ -1982,7 +2004,7 @@ static int launch_bonded(BluesEngine* h, bool with_noise) {
     if (with_noise) { h->noise_draw_base = h->h_draw; h->noise_valid = true; }
     if (B.n_entry_blocks + nb_noise > 0) {
         BondedDyn D; D.draw_base = B.draw_base; D.n_entry_blocks = B.n_entry_blocks;
-        if (h->n_cmap > 0) {   // (CMAP torsions: the instantiations that know both entry-only types)
+        if (h->entry_only_terms()) {   // (CMAP torsions, Urey-Bradley terms, impropers: the instantiations that know every entry-only type)
             if (batch_lead(h)) hipLaunchKernelGGL((k_bonded_entries_b<true, true>), dim3(B.n_entry_blocks + nb_noise, h->batch->R()), dim3(128), 0, h->cur, h->batch->d_core.p, D);
             else if (!batch_dry(h)) hipLaunchKernelGGL((k_bonded_entries<true, true>), dim3(B.n_entry_blocks + nb_noise), dim3(128), 0, h->cur, B);
         }
@@ -2402,8 +2424,8 @@ static int force_pass(BluesEngine* h, int base_L) {
     if ((h->n_cent > 0 || h->pair_mode != BLUES_PAIR_STANDARD) && (h->k1_mode != 4 || h->fuse_forces || h->k2_dense))
         E_FAIL(h, "internal: an engine with custom forces left the decomposed NoCutoff path (k1_mode %d, fuse_forces %d, k2_dense %d)", h->k1_mode, (int)h->fuse_forces, (int)h->k2_dense);
 
-    if (h->n_cmap > 0 && h->fuse_forces)
-        E_FAIL(h, "internal: an engine with CMAP torsions was laid out for the fused force launch, whose bonded body does not know them");
+    if (h->entry_only_terms() && h->fuse_forces)
+        E_FAIL(h, "internal: an engine with CMAP torsions, Urey-Bradley terms or impropers was laid out for the fused force launch, whose bonded body does not know them");
     if (h->n_gen() && (h->fast_step || h->fuse_forces || fin_fusable(h)))
         E_FAIL(h, "internal: an engine with general constraint clusters was laid out for a fused kernel (fast_step %d, fuse_forces %d)", (int)h->fast_step, (int)h->fuse_forces);
 
@@ -2611,7 +2633,7 @@ static EnergyShape energy_shape(const BluesEngine* h) {
     if (h->k1_mode == 3) { g.nw = h->frag_nwg; g.off_frozen = (size_t)2 * h->frag_nwg; }   // one (LJ, Coulomb) pair per workgroup of the fragment kernel
     if (h->k1_mode == 4) { g.nw = h->nc_blocks_e; g.off_frozen = (size_t)2 * h->nc_blocks_e; }   // one (LJ, Coulomb) pair per block of the all-pairs kernel (it has every pair: no frozen-frozen constant)
     if (h->pair_mode == BLUES_PAIR_ETHYLENE) g.nw = 0;   // (the all-pairs kernel is not launched: launch_nocut)
-    int total_terms = h->n_cent + h->n_cmap; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
+    int total_terms = h->n_cent + h->n_cmap + h->n_ub + h->n_impr; for (int ty = 0; ty < T_NTYPES; ty++) total_terms += h->n_terms[ty];
     g.nbb = (total_terms + 255) / 256; g.nfb = (h->n + FROZEN_TILE - 1) / FROZEN_TILE;
     return g;
 }
@@ -2638,7 +2660,7 @@ static int energy_launch(BluesEngine* h) {
     if (launch_pme_exact(h, le)) return 1;
     const EnergyShape g = energy_shape(h);
     if (g.nbb > 0) {
-        if (h->n_cmap > 0) {   // (CMAP torsions: the instantiations that know both entry-only types)
+        if (h->entry_only_terms()) {   // (CMAP torsions, Urey-Bradley terms, impropers: the instantiations that know every entry-only type)
             if (batch_lead(h)) hipLaunchKernelGGL((k_bonded_energy_b<true, true>), dim3(g.nbb, h->batch->R()), dim3(256), 0, h->cur, h->batch->d_core.p);
             else if (!batch_dry(h)) hipLaunchKernelGGL((k_bonded_energy<true, true>), dim3(g.nbb), dim3(256), 0, h->cur, make_bonded_args(h));
         }
@@ -3075,6 +3097,8 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
     if (a->led_flags != b->led_flags) { *why = "measure_shadow_work / measure_heat (measuring and non-measuring members cannot share a batch)"; return false; }
     if (a->pair_mode != b->pair_mode || a->n_cent != b->n_cent) { *why = "custom forces (members with and without the custom pair form or centroid bonds cannot share a batch)"; return false; }
     if (a->n_cmap != b->n_cmap || (a->n_cmap > 0 && a->T != b->T && (a->T->cmap_size != b->T->cmap_size || a->T->cmap_energy != b->T->cmap_energy || a->T->cmap_tor_map != b->T->cmap_tor_map || a->T->cmap_tor_atoms != b->T->cmap_tor_atoms))) { *why = "CMAP torsions (the members' maps or torsions differ)"; return false; }
+    if (a->n_ub != b->n_ub || (a->n_ub > 0 && a->T != b->T && (a->T->ub_atoms != b->T->ub_atoms || a->T->ub_params != b->T->ub_params))) { *why = "Urey-Bradley terms (the members' lists differ)"; return false; }
+    if (a->n_impr != b->n_impr || (a->n_impr > 0 && a->T != b->T && (a->T->impr_atoms != b->T->impr_atoms || a->T->impr_params != b->T->impr_params))) { *why = "impropers (the members' lists differ)"; return false; }
     if (a->pme_exact != b->pme_exact) { *why = "alchemical_pme_treatment (members with the exact and the direct-space treatment cannot share a batch)"; return false; }
     if ((a->gb_model != 0) != (b->gb_model != 0)) { *why = "implicit solvent (members with and without it cannot share a batch)"; return false; }
     if (a->gb_model != b->gb_model || a->gb_eps_in != b->gb_eps_in || a->gb_eps_out != b->gb_eps_out || a->gb_sa_energy != b->gb_sa_energy || a->gb_radius != b->gb_radius || a->gb_scale != b->gb_scale) { *why = "implicit solvent (model, dielectrics, surface term, radii or scales differ)"; return false; }
@@ -3620,7 +3644,7 @@ static void cmap_tables(HostTopology& T) {
 
 static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, const BluesSystemExt* ext) {
     if (ext) {   // alchemical_pme_treatment: what the exact treatment refuses, each with its reason
-        if (ext->struct_size != (int32_t)sizeof(BluesSystemExt) && ext->struct_size != BLUES_SYSTEM_EXT_SIZE_V1) E_FAIL(h, "BluesSystemExt: struct_size %d matches neither this library's %d nor %d (a caller from before the CMAP fields)", ext->struct_size, (int)sizeof(BluesSystemExt), BLUES_SYSTEM_EXT_SIZE_V1);
+        if (ext->struct_size != (int32_t)sizeof(BluesSystemExtV3) && ext->struct_size != (int32_t)sizeof(BluesSystemExt) && ext->struct_size != BLUES_SYSTEM_EXT_SIZE_V1) E_FAIL(h, "BluesSystemExt: struct_size %d matches none of this library's %d (BluesSystemExtV3), %d (BluesSystemExt: maps, no CHARMM terms) and %d (a caller from before the CMAP fields)", ext->struct_size, (int)sizeof(BluesSystemExtV3), (int)sizeof(BluesSystemExt), BLUES_SYSTEM_EXT_SIZE_V1);
         const int tr = ext->alchemical_pme_treatment;
         if (tr != BLUES_ALCH_PME_DIRECT_SPACE && tr != BLUES_ALCH_PME_EXACT) E_FAIL(h, "alchemical_pme_treatment %d: the engine knows 0 ('direct-space') and 1 ('exact')", tr);
         if (tr == BLUES_ALCH_PME_EXACT) {
@@ -3632,7 +3656,7 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
         }
     }
     // CMAP torsion maps (a caller of struct_size 8 has none): what such a System is refused for, each with its reason
-    const bool with_cmap = ext && ext->struct_size == (int32_t)sizeof(BluesSystemExt) && (ext->n_cmap_maps != 0 || ext->n_cmap_torsions != 0);
+    const bool with_cmap = ext && ext->struct_size >= BLUES_SYSTEM_EXT_SIZE_V2 && (ext->n_cmap_maps != 0 || ext->n_cmap_torsions != 0);
     size_t cmap_values = 0;
     if (with_cmap) {
         if (ext->n_cmap_maps < 0 || ext->n_cmap_torsions < 0) E_FAIL(h, "CMAP: %d maps and %d torsions", ext->n_cmap_maps, ext->n_cmap_torsions);
@@ -3648,6 +3672,29 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
             const int32_t* q = ext->cmap_torsion_atoms + 8 * (size_t)t;
             for (int pl = 0; pl < 8; pl++) if (q[pl] < 0 || q[pl] >= s->n_atoms) E_FAIL(h, "CMAP torsion %d: atom index out of range", t);
             for (int d = 0; d < 2; d++) for (int a = 0; a < 4; a++) for (int b = a + 1; b < 4; b++) if (q[4 * d + a] == q[4 * d + b]) E_FAIL(h, "CMAP torsion %d: two equal atoms within one dihedral", t);
+        }
+    }
+    // CHARMM's Urey-Bradley terms and impropers (a caller of struct_size 8 or V2 has none): likewise
+    const BluesSystemExtV3* ext3 = ext && ext->struct_size == (int32_t)sizeof(BluesSystemExtV3) ? reinterpret_cast<const BluesSystemExtV3*>(ext) : nullptr;
+    const bool with_charmm = ext3 && (ext3->n_urey_bradley != 0 || ext3->n_impropers != 0);
+    if (with_charmm) {
+        if (ext3->n_urey_bradley < 0 || ext3->n_impropers < 0) E_FAIL(h, "CHARMM terms: %d Urey-Bradley terms and %d impropers", ext3->n_urey_bradley, ext3->n_impropers);
+        if ((ext3->n_urey_bradley > 0 && (!ext3->urey_bradley_atoms || !ext3->urey_bradley_params)) || (ext3->n_impropers > 0 && (!ext3->improper_atoms || !ext3->improper_params))) E_FAIL(h, "Urey-Bradley terms or impropers without their arrays");
+        for (int t = 0; t < ext3->n_urey_bradley; t++) {
+            const int32_t* q = ext3->urey_bradley_atoms + 2 * (size_t)t;
+            const double r0 = ext3->urey_bradley_params[2 * (size_t)t], k = ext3->urey_bradley_params[2 * (size_t)t + 1];
+            if (q[0] < 0 || q[0] >= s->n_atoms || q[1] < 0 || q[1] >= s->n_atoms) E_FAIL(h, "Urey-Bradley term %d: atom index out of range", t);
+            if (q[0] == q[1]) E_FAIL(h, "Urey-Bradley term %d: two equal atoms within one term", t);
+            if (!std::isfinite(k) || k < 0.0) E_FAIL(h, "Urey-Bradley term %d: force constant %g is negative or not finite", t, k);
+            if (!std::isfinite(r0) || !(r0 > 0.0)) E_FAIL(h, "Urey-Bradley term %d: r0 %g is not a positive length", t, r0);
+        }
+        for (int t = 0; t < ext3->n_impropers; t++) {
+            const int32_t* q = ext3->improper_atoms + 4 * (size_t)t;
+            const double psi0 = ext3->improper_params[2 * (size_t)t], k = ext3->improper_params[2 * (size_t)t + 1];
+            for (int a = 0; a < 4; a++) if (q[a] < 0 || q[a] >= s->n_atoms) E_FAIL(h, "improper %d: atom index out of range", t);
+            for (int a = 0; a < 4; a++) for (int b = a + 1; b < 4; b++) if (q[a] == q[b]) E_FAIL(h, "improper %d: two equal atoms within one term", t);
+            if (!std::isfinite(k) || k < 0.0) E_FAIL(h, "improper %d: force constant %g is negative or not finite", t, k);
+            if (!(fabs(psi0) <= 3.141592653589793)) E_FAIL(h, "improper %d: psi0 %g lies outside [-pi, pi]", t, psi0);
         }
     }
     if (gb && gb->model != BLUES_GB_NONE) {   // implicit solvent (kernels_gb.h): what such an engine refuses, each with its reason
@@ -3729,6 +3776,11 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
             mix(cc, sizeof cc); mix(ext->cmap_size, sizeof(int32_t) * (size_t)ext->n_cmap_maps); mix(ext->cmap_energy, sizeof(double) * cmap_values);
             mix(ext->cmap_torsion_map, sizeof(int32_t) * (size_t)ext->n_cmap_torsions); mix(ext->cmap_torsion_atoms, sizeof(int32_t) * 8 * (size_t)ext->n_cmap_torsions);
         }
+        if (with_charmm) {   // (likewise: a System without these terms keeps the key it had)
+            const int32_t cc[2] = {ext3->n_urey_bradley, ext3->n_impropers};
+            mix(cc, sizeof cc); mix(ext3->urey_bradley_atoms, sizeof(int32_t) * 2 * (size_t)ext3->n_urey_bradley); mix(ext3->urey_bradley_params, sizeof(double) * 2 * (size_t)ext3->n_urey_bradley);
+            mix(ext3->improper_atoms, sizeof(int32_t) * 4 * (size_t)ext3->n_impropers); mix(ext3->improper_params, sizeof(double) * 2 * (size_t)ext3->n_impropers);
+        }
         std::lock_guard<std::mutex> lk(mu);
         auto it = known.find(key);
         if (it != known.end()) h->T = it->second.lock();
@@ -3737,6 +3789,11 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
                                    && h->T->cmap_tor_map == std::vector<int32_t>(ext->cmap_torsion_map, ext->cmap_torsion_map + ext->n_cmap_torsions)
                                    && h->T->cmap_tor_atoms == std::vector<int32_t>(ext->cmap_torsion_atoms, ext->cmap_torsion_atoms + 8 * (size_t)ext->n_cmap_torsions))
                                 : !(h->T->cmap_size.empty() && h->T->cmap_tor_map.empty()))) h->T.reset();
+        if (h->T && (with_charmm ? !(h->T->ub_atoms == std::vector<int32_t>(ext3->urey_bradley_atoms, ext3->urey_bradley_atoms + 2 * (size_t)ext3->n_urey_bradley)
+                                     && h->T->ub_params == std::vector<double>(ext3->urey_bradley_params, ext3->urey_bradley_params + 2 * (size_t)ext3->n_urey_bradley)
+                                     && h->T->impr_atoms == std::vector<int32_t>(ext3->improper_atoms, ext3->improper_atoms + 4 * (size_t)ext3->n_impropers)
+                                     && h->T->impr_params == std::vector<double>(ext3->improper_params, ext3->improper_params + 2 * (size_t)ext3->n_impropers))
+                                  : !(h->T->ub_atoms.empty() && h->T->impr_atoms.empty()))) h->T.reset();
         if (!h->T) {
             auto T = std::make_shared<HostTopology>();
             T->mass.assign(s->mass, s->mass + n); T->charge.assign(s->charge, s->charge + n); T->sigma.assign(s->sigma, s->sigma + n); T->eps.assign(s->epsilon, s->epsilon + n);
@@ -3754,6 +3811,10 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
                 T->cmap_size.assign(ext->cmap_size, ext->cmap_size + ext->n_cmap_maps); T->cmap_energy.assign(ext->cmap_energy, ext->cmap_energy + cmap_values);
                 T->cmap_tor_map.assign(ext->cmap_torsion_map, ext->cmap_torsion_map + ext->n_cmap_torsions); T->cmap_tor_atoms.assign(ext->cmap_torsion_atoms, ext->cmap_torsion_atoms + 8 * (size_t)ext->n_cmap_torsions);
                 cmap_tables(*T);
+            }
+            if (with_charmm) {
+                T->ub_atoms.assign(ext3->urey_bradley_atoms, ext3->urey_bradley_atoms + 2 * (size_t)ext3->n_urey_bradley); T->ub_params.assign(ext3->urey_bradley_params, ext3->urey_bradley_params + 2 * (size_t)ext3->n_urey_bradley);
+                T->impr_atoms.assign(ext3->improper_atoms, ext3->improper_atoms + 4 * (size_t)ext3->n_impropers); T->impr_params.assign(ext3->improper_params, ext3->improper_params + 2 * (size_t)ext3->n_impropers);
             }
             h->T = T; known[key] = T;
             for (auto q = known.begin(); q != known.end();) { if (q->second.expired()) q = known.erase(q); else ++q; }

@@ -1,5 +1,6 @@
 // kernels_bonded.h -- harmonic bonds/angles, periodic torsions, env-env 1-4 exceptions, the
-// positional restraint, harmonic centroid bonds and CMAP torsion correction maps (K3/K4), fp64, gather form.
+// positional restraint, harmonic centroid bonds, CMAP torsion correction maps and CHARMM's Urey-Bradley terms and harmonic
+// impropers (K3/K4), fp64, gather form.
 //
 // OpenMM's HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce / NonbondedForce
 // exceptions / CustomExternalForce('k_restr*periodicdistance(x,y,z,x0,y0,z0)^2',
@@ -20,6 +21,14 @@ enum { T_CENT = T_NTYPES };   // (the first value past the per-type arrays; blue
 // System.  Terms in arrays of their own (BondedArgs::cmap_*), energy booked with the torsions', known to the CMAP = true instantiations only.
 enum { T_CMAP = T_NTYPES + 1 };
 #define CMAP_TWO_PI 6.283185307179586476925286766559
+// CHARMM's Urey-Bradley 1-3 terms (T_BOND's form between the outer atoms of an angle; energy booked with the bonds') and harmonic
+// impropers (E = k (psi - psi0)^2 over T_TORSION's dihedral; energy booked with the torsions'): two more ENTRY-only types, terms in
+// arrays of their own (BondedArgs::ub_* / impr_*).  They have no template flag of their own: they ride with CMAP = true, which now reads
+// "knows every entry-only type that can sit on any System".  A chamber topology carries maps and these terms together, a fourth flag
+// would double the instantiations (lone, batched, entries, energy) for a branch the CMAP = true kernels skip in two compares, and the
+// CMAP = false instantiations -- what every System without maps and without these terms launches -- stay the code they were.
+enum { T_UREY = T_NTYPES + 2, T_IMPR = T_NTYPES + 3 };
+#define IMPR_PI 3.141592653589793238462643383279
 
 struct BondedArgs {
     int n_rows;
@@ -51,6 +60,9 @@ struct BondedArgs {
     // CMAP torsions: 8 atoms per term; cmap_grid[2 t] = n of the term's map, [2 t + 1] = its first patch in cmap_coef, which holds 16
     // doubles per patch (i + n * j): c[a][b] of E = sum c[a][b] t^a u^b, t = phi / delta - i, u = psi / delta - j
     int n_cmap; const int* cmap_atoms; const int* cmap_grid; const double* cmap_coef;
+    // Urey-Bradley terms: 2 atoms and (r0, k) per term; impropers: 4 atoms and (psi0, k) per term
+    int n_ub; const int* ub_atoms; const double* ub_params;
+    int n_impr; const int* impr_atoms; const double* impr_params;
 };
 
 __device__ inline void mi3(const BondedArgs& B, double d[3]) {
@@ -63,7 +75,7 @@ __device__ inline double dot3(const double a[3], const double b[3]) { return a[0
 
 // ---- CMAP: the dihedral of T_TORSION below (same vectors, sign rule and minimum image) shifted into [0, 2 pi], with what its
 // position gradient needs
-struct CmapDihedral { double m[3], nn[3], m2, n2, lkj, p, qq, phi; };
+struct CmapDihedral { double m[3], nn[3], m2, n2, lkj, p, qq, phi, raw; };   // (raw: the angle in (-pi, pi], before the shift)
 __device__ inline void cmap_dihedral(const BondedArgs& B, const int* q, CmapDihedral& D) {
     double rij[3], rkj[3], rkl[3];
     for (int c = 0; c < 3; c++) { rij[c] = B.x[c][q[0]] - B.x[c][q[1]]; rkj[c] = B.x[c][q[2]] - B.x[c][q[1]]; rkl[c] = B.x[c][q[2]] - B.x[c][q[3]]; }
@@ -75,7 +87,7 @@ __device__ inline void cmap_dihedral(const BondedArgs& B, const int* q, CmapDihe
     // T_TORSION's angle -- cos = m.n / |m||n|, negative where rij.n < 0 -- taken as atan2(|rkj| rij.n, m.n): the same angle with the same
     // sign rule, but acos loses half its digits near 0 and pi (1e-8 rad), and here the angle picks the patch and the place within it
     const double phi = atan2(D.lkj * dot3(rij, D.nn), dot3(D.m, D.nn));
-    D.phi = phi < 0.0 ? phi + CMAP_TWO_PI : phi;
+    D.phi = phi < 0.0 ? phi + CMAP_TWO_PI : phi; D.raw = phi;
     D.p = dot3(rij, rkj) / lkj2; D.qq = dot3(rkl, rkj) / lkj2;
 }
 // F += -ddphi * d(phi)/d(x of the atom in `role`): T_TORSION's fi, fl, sv expressions
@@ -117,12 +129,37 @@ __device__ inline double cmap_term(const BondedArgs& B, const int idx, const int
     return e;
 }
 
+// ---- Urey-Bradley: T_BOND's expressions over the term's own arrays (minimum image, E = 0.5 k (r - r0)^2)
+__device__ inline double urey_bradley_term(const BondedArgs& B, const int idx, const int role, double F[3]) {
+    const int i = B.ub_atoms[2 * idx], j = B.ub_atoms[2 * idx + 1];
+    const double r0 = B.ub_params[2 * idx], k = B.ub_params[2 * idx + 1];
+    double d[3] = {B.x[0][i] - B.x[0][j], B.x[1][i] - B.x[1][j], B.x[2][i] - B.x[2][j]};
+    mi3(B, d);
+    const double r = sqrt(dot3(d, d)), dr = r - r0, fs = -k * dr / r;
+    const double sgn = role == 0 ? 1.0 : -1.0;
+    if (role >= 0) for (int c = 0; c < 3; c++) F[c] = sgn * fs * d[c];
+    return 0.5 * k * dr * dr;
+}
+// ---- harmonic improper: E = k delta^2, delta = psi - psi0 wrapped into (-pi, pi], psi the dihedral 1-2-3-4 through atan2 (the terms sit
+// at psi ~ psi0 = 0, where acos keeps half its digits and the energy is quadratic in the angle); dE/dpsi = 2 k delta, distributed as T_TORSION's
+__device__ inline double improper_term(const BondedArgs& B, const int idx, const int role, double F[3]) {
+    CmapDihedral D;
+    cmap_dihedral(B, B.impr_atoms + 4 * idx, D);
+    const double psi0 = B.impr_params[2 * idx], k = B.impr_params[2 * idx + 1];
+    double delta = D.raw - psi0;
+    delta = delta > IMPR_PI ? delta - CMAP_TWO_PI : (delta <= -IMPR_PI ? delta + CMAP_TWO_PI : delta);
+    if (role >= 0) cmap_project(D, 2.0 * k * delta, role, F);
+    return k * delta * delta;
+}
+
 // energy of term (type, idx); if role >= 0 also the force on the atom in that role
 template <bool CENT = false, bool CMAP = false>
 __device__ inline double bonded_term(const BondedArgs& B, int type, int idx, int role, double F[3]) {
     F[0] = F[1] = F[2] = 0.0;
     if constexpr (CMAP) {
         if (type == T_CMAP) return cmap_term(B, idx, role, F);
+        if (type == T_UREY) return urey_bradley_term(B, idx, role, F);
+        if (type == T_IMPR) return improper_term(B, idx, role, F);
     }
     if constexpr (CENT) {
         if (type == T_CENT) {  // E = 0.5 k |c1 - c2|^2, c = sum(w x) / sum(w): explicit weights, summed in the groups' order; never periodic
@@ -259,7 +296,8 @@ __global__ void __launch_bounds__(128) k_bonded_entries(BondedArgs B) { bonded_e
 
 // energy of every term (frozen ones included): per-block partial sums per type
 // (CENT: the centroid bonds follow the six types; their energy goes into the restraint's partial -- both are energy term 7;
-//  CMAP: the CMAP torsions follow those; their energy goes into the torsions' partial -- both are energy term 2)
+//  CMAP: the CMAP torsions follow those; their energy goes into the torsions' partial -- both are energy term 2; then the
+//  Urey-Bradley terms, into the bonds' partial -- energy term 0 --, and the impropers, into the torsions')
 template <bool CENT = false, bool CMAP = false>
 __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
     const int gid = blockIdx.x * 256 + threadIdx.x;
@@ -278,6 +316,12 @@ __device__ __forceinline__ void bonded_energy_body(const BondedArgs& B) {
     if constexpr (CMAP) {
         const int idx = gid - base;
         if (idx >= 0 && idx < B.n_cmap) { double F[3]; e[T_TORSION] += cmap_term(B, idx, -1, F); }
+        base += B.n_cmap;
+        const int iu = gid - base;
+        if (iu >= 0 && iu < B.n_ub) { double F[3]; e[T_BOND] += urey_bradley_term(B, iu, -1, F); }
+        base += B.n_ub;
+        const int ii = gid - base;
+        if (ii >= 0 && ii < B.n_impr) { double F[3]; e[T_TORSION] += improper_term(B, ii, -1, F); }
     }
     __shared__ double s[4][T_NTYPES];
     for (int ty = 0; ty < T_NTYPES; ty++) { double v = wave_sum(e[ty]); if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6][ty] = v; }

@@ -27,6 +27,7 @@ class NativeEngine:
             system.check_implicit_solvent(integrator)
             system.check_alchemical_pme_treatment(integrator)
             system.check_cmap()
+            system.check_charmm()
         except ValueError as e:
             raise EngineError(str(e))
         self._lib = load()

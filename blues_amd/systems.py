@@ -22,6 +22,7 @@ _ARRAY_FIELDS = ("box", "mass", "charge", "sigma", "epsilon", "exclusions", "exc
 _SCALAR_FIELDS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha",
                   "annihilate_electrostatics", "annihilate_sterics", "remove_cm_motion")
 _OPTIONAL_SCALARS = ("pme_order", "dispersion_correction")   # (files written before reciprocal space existed do not have them)
+_CHARMM_FIELDS = ("urey_bradley_atoms", "urey_bradley_params", "improper_atoms", "improper_params")   # SystemData's Urey-Bradley terms and impropers
 _GB_FIELDS = ("model", "radius", "scale", "solute_dielectric", "solvent_dielectric", "surface_area_energy")   # SystemData.implicit_solvent, stored as gb_<field>
 
 
@@ -37,6 +38,8 @@ def save_system(path, system: SystemData, **extra):
         d["cmap_torsions"] = np.asarray(system.cmap_torsions, dtype=np.int32).reshape(-1, 9)
         d["cmap_n_maps"] = np.asarray(len(system.cmap_maps), dtype=np.int32)
         d.update({"cmap_map_%d" % k: np.asarray(m, dtype=np.float64) for k, m in enumerate(system.cmap_maps)})
+    if system.has_charmm:   # (likewise)
+        d.update({k: np.asarray(getattr(system, k)) for k in _CHARMM_FIELDS})
     d.update({k: np.asarray(v) for k, v in extra.items()})
     np.savez_compressed(path, **d)
 
@@ -60,6 +63,7 @@ def load_system(path):
     if "cmap_n_maps" in z.files:
         kw["cmap_maps"] = tuple(z["cmap_map_%d" % k] for k in range(int(z["cmap_n_maps"])))
         kw["cmap_torsions"] = z["cmap_torsions"]
+    kw.update({k: z[k] for k in _CHARMM_FIELDS if k in z.files})
     extra = {k: z[k] for k in z.files if k not in kw and not k.startswith("gb_") and not k.startswith("cmap_")}
     return SystemData(**kw), extra
 
@@ -197,6 +201,8 @@ def tile_system(system: SystemData, reps):
         implicit_solvent=None if system.implicit_solvent is None else system.implicit_solvent.subset(np.tile(np.arange(n), ncopy)),
         alchemical_pme_treatment=system.alchemical_pme_treatment,
         cmap_maps=tuple(system.cmap_maps or ()), cmap_torsions=_tile_cmap_torsions(system.cmap_torsions, n, ncopy),
+        urey_bradley_atoms=rep_idx(system.urey_bradley_atoms), urey_bradley_params=rep_val(system.urey_bradley_params),
+        improper_atoms=rep_idx(system.improper_atoms), improper_params=rep_val(system.improper_params),
     )
 
 
@@ -304,6 +310,8 @@ def assemble_s23k_solute(base: SystemData, vel, removed_waters, inserted_x, inse
     bond_a, bond_p = terms(base.bond_atoms, base.bond_params)
     ang_a, ang_p = terms(base.angle_atoms, base.angle_params)
     tor_a, tor_p = terms(base.torsion_atoms, base.torsion_params)
+    ub_a, ub_p = terms(base.urey_bradley_atoms, base.urey_bradley_params)
+    imp_a, imp_p = terms(base.improper_atoms, base.improper_params)
     con_a, con_d = terms(base.constraint_atoms, np.asarray(base.constraint_dist).reshape(-1, 1))
     pos = np.concatenate([base.positions[lig], np.asarray(inserted_x, np.float64).reshape(-1, 3), base.positions[keep_rest]])
     v = None
@@ -318,7 +326,9 @@ def assemble_s23k_solute(base: SystemData, vel, removed_waters, inserted_x, inse
         alchemical_atoms=np.arange(n_lig, dtype=np.int32), nonbonded_method=base.nonbonded_method, cutoff=base.cutoff, ewald_alpha=base.ewald_alpha,
         softcore_alpha=base.softcore_alpha, annihilate_electrostatics=base.annihilate_electrostatics, annihilate_sterics=base.annihilate_sterics,
         remove_cm_motion=base.remove_cm_motion, pme_order=base.pme_order, dispersion_correction=base.dispersion_correction, positions=pos,
-        residue_of_atom=new_res.astype(np.int32), alchemical_pme_treatment=base.alchemical_pme_treatment)
+        residue_of_atom=new_res.astype(np.int32), alchemical_pme_treatment=base.alchemical_pme_treatment,
+        urey_bradley_atoms=ub_a.reshape(-1, 2), urey_bradley_params=np.asarray(ub_p, np.float64).reshape(-1, 2),
+        improper_atoms=imp_a.reshape(-1, 4), improper_params=np.asarray(imp_p, np.float64).reshape(-1, 2))
     assert s.n_atoms == n
     return s, v
 
@@ -365,7 +375,7 @@ def dispersion_correction_energy(system: SystemData, zero_epsilon=()):
 
 
 _FORCE_FIELD_ARRAYS = ("charge", "sigma", "epsilon", "exclusions", "exception_atoms", "exception_params", "bond_atoms", "bond_params", "angle_atoms",
-                       "angle_params", "torsion_atoms", "torsion_params", "restraint_atoms", "restraint_x0")
+                       "angle_params", "torsion_atoms", "torsion_params", "restraint_atoms", "restraint_x0") + _CHARMM_FIELDS
 _FORCE_FIELD_SCALARS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha", "pme_order", "dispersion_correction")
 
 

@@ -226,8 +226,23 @@ int blues_engine_create_gb(const BluesSystemDesc *sys, const BluesIntegratorDesc
 #define BLUES_CMAP_MIN_SIZE 4
 #define BLUES_CMAP_MAX_SIZE 64
 #define BLUES_SYSTEM_EXT_SIZE_V1 8      /* struct_size of a caller from before the CMAP fields: it has no maps */
+/* CHARMM's Urey-Bradley terms and harmonic impropers: what createSystem makes of a chamber topology's CHARMM_UREY_BRADLEY* and
+ * CHARMM_IMPROPERS* sections (a HarmonicBondForce and a CustomTorsionForce; reference blues/settings.py:60-90, blues/simulation.py:139-219).
+ * Additive to ABI 9.
+ *   Urey-Bradley  two atoms, r0 (nm) and k (kJ/mol/nm^2): E = 0.5 k (r - r0)^2 with the minimum image of a harmonic bond.  It is a force
+ *                 between the outer atoms of an angle, NOT a bond: it joins no molecule (barostat, wrapping), fragment or constraint
+ *                 cluster, which is why it is not a row of bond_atoms.  Booked with energy term [0].
+ *   improper      four atoms, psi0 (rad, |psi0| <= pi) and k (kJ/mol/rad^2): E = k d^2, d = psi - psi0 wrapped into (-pi, pi], psi the
+ *                 dihedral of atoms 1-2-3-4 exactly as a periodic torsion takes it (vectors, sign, minimum image).  Collinear atoms
+ *                 are as undefined as they are there.  Booked with energy term [2].
+ * Neither term is alchemical: the same in all three lambda slots, nothing added to protocol work, full strength on alchemical atoms.
+ * Creation fails, with the reason, for a negative count, a count without its arrays, an atom out of range, two equal atoms within a
+ * term, a k that is negative or not finite, r0 <= 0 and |psi0| > pi. */
+#define BLUES_SYSTEM_EXT_SIZE_V2 56     /* sizeof(BluesSystemExt) on LP64: struct_size of a caller with maps but no CHARMM terms */
 typedef struct BluesSystemExt {
-    int32_t struct_size;                 /* sizeof(BluesSystemExt) of the caller: 8 (a caller from before the maps: none) or this struct's */
+    int32_t struct_size;                 /* what the caller passes: sizeof(BluesSystemExtV3) (below: everything is read), sizeof(BluesSystemExt)
+                                          * = BLUES_SYSTEM_EXT_SIZE_V2 (this struct) or BLUES_SYSTEM_EXT_SIZE_V1 (the first two fields);
+                                          * anything else is refused */
     int32_t alchemical_pme_treatment;    /* BLUES_ALCH_PME_* */
     int32_t n_cmap_maps;
     const int32_t *cmap_size;            /* [n_cmap_maps] n of every map */
@@ -236,7 +251,26 @@ typedef struct BluesSystemExt {
     const int32_t *cmap_torsion_map;    /* [n_cmap_torsions] */
     const int32_t *cmap_torsion_atoms;   /* [8 * n_cmap_torsions] a1..a4, b1..b4 */
 } BluesSystemExt;
-/* ext = NULL: blues_engine_create_gb */
+/* The descriptor grown at its end by the CHARMM terms: BluesSystemExt's fields at BluesSystemExt's offsets, the new ones behind them.
+ * BluesSystemExt itself keeps its layout and size, so a caller compiled against it stays what it was.  A caller with such terms fills
+ * this struct, sets struct_size = sizeof(BluesSystemExtV3) and passes (const BluesSystemExt *)&ext to blues_engine_create_ext. */
+typedef struct BluesSystemExtV3 {
+    int32_t struct_size;                 /* sizeof(BluesSystemExtV3) */
+    int32_t alchemical_pme_treatment;
+    int32_t n_cmap_maps;
+    const int32_t *cmap_size;
+    const double *cmap_energy;
+    int32_t n_cmap_torsions;
+    const int32_t *cmap_torsion_map;
+    const int32_t *cmap_torsion_atoms;
+    int32_t n_urey_bradley;              /* (offset BLUES_SYSTEM_EXT_SIZE_V2) */
+    const int32_t *urey_bradley_atoms;   /* [2 * n_urey_bradley] */
+    const double *urey_bradley_params;   /* [2 * n_urey_bradley] r0, k */
+    int32_t n_impropers;
+    const int32_t *improper_atoms;       /* [4 * n_impropers] */
+    const double *improper_params;       /* [2 * n_impropers] psi0, k */
+} BluesSystemExtV3;
+/* ext = NULL: blues_engine_create_gb; ext->struct_size says which of the two structs (or the 8-byte head) ext points to */
 int blues_engine_create_ext(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, const BluesImplicitSolventDesc *gb, const BluesSystemExt *ext, int device, BluesEngine **out);
 /* (phi, psi) of every CMAP torsion at the engine's current device positions, radians in [0, 2 pi): what a Ramachandran reporter
  * reads.  Additive to ABI 9; a library without it loads, and only a System with maps needs it. */
