@@ -298,6 +298,7 @@ struct BluesEngine {
     std::vector<int> mobile;       // caller indices with mass > 0
     std::vector<HostCluster> clusters;
     int n_itiles = 0, n_tiles = 0, jcap = 0, n_islots = 0, pool_cap = 0, PA = 1, k2_nblocks_env = 0, k2_jiter = 1;
+    int n_exc_ent = 0;       // entries of the alchemical exception rows (d_exc_partner; blues_get_alchemical_layout)
     bool k2_dense = false;   // the alchemical kernel's env pairs in their dense form (kernels_alch.h: alchemical_dense_body)
     bool k2_f32 = false;     // ... in fp32 pair arithmetic with the work from per-pair differences (alchemical_dense32_body; round 6)
     int seg_len = 64, waves_tile = 4, wpb = 4, npart = 1;  // K1 decomposition
@@ -960,6 +961,7 @@ static int build_bonded(BluesEngine* h, const BluesSystemDesc* s) {
     for (size_t a = 0; a < h->alch.size(); a++) { eo.insert(eo.end(), arow_partner[a].size(), h->alch[a]); ep.insert(ep.end(), arow_partner[a].begin(), arow_partner[a].end()); epar.insert(epar.end(), arow_par[a].begin(), arow_par[a].end()); es.push_back((int)ep.size()); }
     { std::vector<int> ie(ep.size()); for (size_t q = 0; q < ep.size(); q++) ie[q] = h->T->alch_local[ep[q]] < 0; h->d_exc_is_env.upload(ie); }
     h->d_exc_start.upload(es); h->d_exc_partner.upload(ep); h->d_exc_owner.upload(eo); h->d_exc_params.upload(epar);
+    h->n_exc_ent = (int)ep.size();
     return 0;
 }
 
@@ -1864,7 +1866,11 @@ static AlchArgs make_alch_args(BluesEngine* h, const double ls[3], const double 
 static AlchDyn make_alch_dyn(const AlchArgs& A) { AlchDyn d; for (int s = 0; s < 3; s++) { d.ls[s] = A.ls[s]; d.le[s] = A.le[s]; } d.slot_mask = A.slot_mask; return d; }
 
 // part (a batch's leader with a dense alchemical kernel only): 0 both of its kernels; 3 ... 6 one of them, see below
-static int launch_alchemical(BluesEngine* h, const double ls[3], const double le[3], int slot_mask, int part = 0) {
+// energy: the launch of an energy evaluation (energy_launch).  An engine on the fp32 dense form takes the fp64 dense body for it: the
+// fp32 form's pair energies are good to ~2^-22 of the sum of their magnitudes, which protects the work of a step (formed from per-pair
+// differences) but not a term that is the small remainder of large cancelling Coulomb energies -- an alchemical water's -0.222 kJ/mol
+// came out 1.3e-5 off where the terms are held to 1e-5 max(|term|, 1).  Same lists, same slabs; force passes are not affected.
+static int launch_alchemical(BluesEngine* h, const double ls[3], const double le[3], int slot_mask, int part = 0, bool energy = false) {
     if (h->alch.empty()) return 0;
     AlchArgs A = make_alch_args(h, ls, le, slot_mask);
     const bool fast = h->precision == 0;
@@ -1872,7 +1878,7 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
         // dense env pairs: one workgroup per chain; the alchemical x alchemical block is the other kernel's (a grid of self blocks only)
         if (batch_dry(h)) { h->st_launches++; return 0; }
         const bool lead = batch_lead(h);
-        if (h->k2_f32) {
+        if (h->k2_f32 && !energy) {
             // the fp32 form (kernels_alch.h: alchemical_dense32_body): its LDS record depends on how many force slots the pass produces
             static thread_local bool opened32[2] = {false, false};
             if (!opened32[lead]) {
@@ -2652,7 +2658,7 @@ static int energy_launch(BluesEngine* h) {
     h->lists_forced = false;
     if (rc) return 1;
     h->pass_valid = false;  // slabs are about to be overwritten with parameters that are not a regular pass
-    if (launch_alchemical(h, ls, le, 1)) return 1;
+    if (launch_alchemical(h, ls, le, 1, 0, true)) return 1;
     rc = launch_nonbonded_p<true>(h);
     if (rc) return 1;
     if (h->gb_model && launch_gb_p<true>(h, le)) return 1;
@@ -4720,6 +4726,23 @@ int blues_get_pme_path(BluesEngine* h, int64_t out[2]) {
     HIP_OK(h, hipStreamSynchronize(h->stream));   // (a batch member's launches ran on the batch's stream, which a batch call waits for before it returns)
     HIP_OK(h, hipMemcpy(c, h->d_pme_path.p, sizeof c, hipMemcpyDeviceToHost));
     out[0] = c[0]; out[1] = c[1];
+    return 0;
+}
+
+int blues_get_alchemical_layout(BluesEngine* h, int64_t out[4]) {
+    out[0] = h->alch.empty() ? 0 : h->PA; out[1] = h->alch.empty() ? 0 : h->k2_jiter; out[2] = 0; out[3] = h->n_exc_ent;
+    if (h->alch.empty() || !h->sorted_ok || !h->d_jcount.p) return 0;
+    hipSetDevice(h->device);
+    HIP_OK(h, hipStreamSynchronize(h->stream));
+    if (h->k1_mode != 4) {   // (NoCutoff: the list is every environment atom, written with the layout; otherwise a build must have run)
+        if (!h->d_flags.p) return 0;
+        DevFlags f;
+        HIP_OK(h, hipMemcpy(&f, h->d_flags.p, sizeof f, hipMemcpyDeviceToHost));
+        if (f.builds <= 0) return 0;
+    }
+    int c = 0;
+    HIP_OK(h, hipMemcpy(&c, h->d_jcount.p + h->n_lists, sizeof c, hipMemcpyDeviceToHost));
+    out[2] = c;
     return 0;
 }
 

@@ -76,8 +76,8 @@ __device__ inline bool excluded_sorted(const int* ex_start, const int* ex_idx, i
 // Both lambdas move the 12-6 part, so it is formed per slot from ls[s] AND le[s] and lands in the per-slot sterics S0..S2 (neither
 // shortcut of the FAST path holds); q / r^2 depends on no lambda and lands in const_coul.  sig = 0 gives an exact 0, no softcore is
 // needed.  The alchemical x alchemical pairs do not interact in this form: the last block evaluates the exception rows only.
-// Energies fp64 in both precisions (they are the protocol work); the force scale is formed in fp64 with them and its components are
-// FT, as in the env blocks of form 0.
+// Energies fp64 in both precisions (they are the protocol work); the force scale and its components are fp64 too,
+// as in the env blocks of form 0.
 // Returns false when the (env) block had no list entries left, i.e. every later block is empty too.
 template <bool FAST, int MASK = -1, int FORM = 0>
 __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id) {
@@ -88,14 +88,13 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
     __shared__ double s_self[4][9][64];
     __shared__ double s_e[4][K2_NE];
     __shared__ double s_exc[9][256];   // self block: exception rows; env blocks: the block's j records and positions (K2_STAGE entries)
-    // Force arithmetic of the env blocks: fp32 in the mixed mode (FAST) -- the force scale of a pair is formed in fp64 with its
-    // energy and rounded once; its three components, the sum over the alchemical lanes (force on j) and the running sum over
-    // this thread's j's (force on a) are fp32; block partials are fp64 again.  The ENERGIES -- the protocol work -- stay fp64
-    // throughout.  Half the live registers of the loop were these fp64 force values.
-    using FT = typename std::conditional<FAST, float, double>::type;
-    FT f[3][3];  // [slot][xyz] force on the alchemical atom from this pair
+    // Force arithmetic of the env blocks: fp64 in both modes, like the energies (the protocol work).  The mixed mode (FAST) once kept a
+    // pair force's three components and their sums in fp32: one rounding of a component of 3.5e3 kJ/mol/nm -- a hydrogen bond of an
+    // alchemical water -- is up to 1.2e-4, and the lane layout and the fp64 dense body, which sum in different orders, then differed by
+    // 1.5e-4 to 3.8e-4 where 1e-8 of the largest force + 2e-5 is asked (tests/test_gpu_alch_regions.py).
+    double f[3][3];  // [slot][xyz] force on the alchemical atom from this pair
 #pragma unroll
-    for (int s = 0; s < 3; s++) { f[s][0] = f[s][1] = f[s][2] = (FT)0; }
+    for (int s = 0; s < 3; s++) { f[s][0] = f[s][1] = f[s][2] = 0.0; }
     double e[K2_NE];
 #pragma unroll
     for (int q = 0; q < K2_NE; q++) e[q] = 0.0;
@@ -122,9 +121,9 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
         if (a < A.n_alch) { Ar.ao = g_arec[a].ao; Ar.asrt = g_arec[a].asrt; Ar.has_env_excl = g_arec[a].has_env_excl; Ar.sig = g_arec[a].sig; Ar.eps = g_arec[a].eps; Ar.q = g_arec[a].q; }
         double xa[3] = {0.0, 0.0, 0.0};
         if (a < A.n_alch) { xa[0] = g_x0[Ar.ao]; xa[1] = g_x1[Ar.ao]; xa[2] = g_x2[Ar.ao]; }
-        FT fa[3][3];
+        double fa[3][3];
 #pragma unroll
-        for (int s = 0; s < 3; s++) { fa[s][0] = fa[s][1] = fa[s][2] = (FT)0; }
+        for (int s = 0; s < 3; s++) { fa[s][0] = fa[s][1] = fa[s][2] = 0.0; }
         wave_hit = false;
         // The block's j records and their positions are staged in LDS by one round of loads (record -> position: two dependent
         // memory round trips per BLOCK; read per pair they were two per iteration, and with three waves per SIMD the kernel
@@ -150,7 +149,7 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
             bool hit = false;  // this lane holds a pair term
             bool j_mobile = false;
 #pragma unroll
-            for (int s = 0; s < 3; s++) { f[s][0] = f[s][1] = f[s][2] = (FT)0; }
+            for (int s = 0; s < 3; s++) { f[s][0] = f[s][1] = f[s][2] = 0.0; }
             if (valid) {
                 AlchJRec J; J.jsrt = st_jsrt[sl]; J.jo = st_jo[sl]; J.sig = st_sig[sl]; J.eps = st_eps[sl]; J.q = st_q[sl];
                 jsrt = J.jsrt & 0x3fffffff; j_mobile = (J.jsrt >> 30) & 1;
@@ -174,8 +173,8 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                             const double sr2 = sg * sg * inv_r2, sr6 = sr2 * sr2 * sr2;
                             e[1 + s] += ep4 * (sr6 * sr6 - sr6);
                             if (MASK >= 0 && !((MASK >> s) & 1)) continue;
-                            const FT ft = (FT)(fc + ep4 * (12.0 * sr6 * sr6 - 6.0 * sr6) * inv_r2);
-                            f[s][0] = ft * (FT)d[0]; f[s][1] = ft * (FT)d[1]; f[s][2] = ft * (FT)d[2];
+                            const double ft = fc + ep4 * (12.0 * sr6 * sr6 - 6.0 * sr6) * inv_r2;
+                            f[s][0] = ft * d[0]; f[s][1] = ft * d[1]; f[s][2] = ft * d[2];
                         }
                     } else if (FAST && A.pme) {
                         // Two things the schedule makes common (reference blues/simulation.py:654-659: sterics move only for
@@ -191,8 +190,8 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                         for (int s = 0; s < 3; s++) {
                             e[1 + s] += es[s];
                             if (MASK >= 0 && !((MASK >> s) & 1)) continue;
-                            const FT ft = (FT)(fs3[s] + A.le[s] * fc);
-                            f[s][0] = ft * (FT)d[0]; f[s][1] = ft * (FT)d[1]; f[s][2] = ft * (FT)d[2];
+                            const double ft = fs3[s] + A.le[s] * fc;
+                            f[s][0] = ft * d[0]; f[s][1] = ft * d[1]; f[s][2] = ft * d[2];
                         }
                     } else {
                         e[0] += coulomb_d(r2, qq, A.alpha, A.pme != 0, &fc);
@@ -201,7 +200,7 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                             double fs;
                             e[1 + s] += softcore_lj_d(r2, sig, eps, A.ls[s], A.sc_alpha, &fs);
                             const double ft = fs + A.le[s] * fc;
-                            f[s][0] = (FT)(ft * d[0]); f[s][1] = (FT)(ft * d[1]); f[s][2] = (FT)(ft * d[2]);
+                            f[s][0] = ft * d[0]; f[s][1] = ft * d[1]; f[s][2] = ft * d[2];
                         }
                     }
                 } else if (excl) {
@@ -220,7 +219,7 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                             double fs;
                             e[1 + s] += softcore_lj_d(r2, sig, eps, A.ls[s], A.sc_alpha, &fs);
                             const double ft = fs + A.le[s] * fc;
-                            f[s][0] = (FT)(ft * d[0]); f[s][1] = (FT)(ft * d[1]); f[s][2] = (FT)(ft * d[2]);
+                            f[s][0] = ft * d[0]; f[s][1] = ft * d[1]; f[s][2] = ft * d[2];
                         }
                     }
                 }
@@ -237,7 +236,7 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                 if (!slot_on(s)) continue;
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
-                    const FT fj = group_fj ? seg_sum(f[s][k], PA) : (FT)0;
+                    const double fj = group_fj ? seg_sum(f[s][k], PA) : 0.0;
                     if (a == 0 && j_mobile) g_fJ[(size_t)(s * 3 + k) * A.n + jsrt] = -(double)fj;
                     fa[s][k] += f[s][k];
                 }
@@ -346,7 +345,7 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
         for (int s = 0; s < 3; s++)
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-                FT v = (FT)0;
+                double v = 0.0;
                 if (slot_on(s)) {   // a slot whose force nobody applies is not reduced (its energy still is)
                     v = f[s][k];
                     for (int off = PA; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
@@ -551,9 +550,9 @@ __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
             // per lane across the items and over the wave once per atom (round 3 reduced nine values over the wave after EVERY item:
             // a quarter of the loop's instructions).  The sums land in fixed-point accumulators: any order gives the same bits.
             const int per_wave = (nitems + K2D_WAVES - 1) / K2D_WAVES, item_lo = wv * per_wave, item_hi = min(nitems, item_lo + per_wave);
-            float facc[3][3];
+            double facc[3][3];   // (fp64 like the lane layout's: the two fp64 forms agree to the fixed point's resolution)
 #pragma unroll
-            for (int s = 0; s < 3; s++) { facc[s][0] = facc[s][1] = facc[s][2] = 0.0f; }
+            for (int s = 0; s < 3; s++) { facc[s][0] = facc[s][1] = facc[s][2] = 0.0; }
             int acc_a = -1;
             auto flush = [&]() {
                 if (acc_a < 0) return;
@@ -562,9 +561,9 @@ __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
                     if (!slot_on(s)) continue;
 #pragma unroll
                     for (int c3 = 0; c3 < 3; c3++) {
-                        const float v = wave_sum_dpp_f32(facc[s][c3]);
-                        if (lane == 0) atomicAdd(&S.fa[s * 3 + c3][acc_a], (unsigned long long)__double2ll_rn((double)v * K2D_FIX));
-                        facc[s][c3] = 0.0f;
+                        const double v = wave_sum(facc[s][c3]);
+                        if (lane == 0) atomicAdd(&S.fa[s * 3 + c3][acc_a], (unsigned long long)__double2ll_rn(v * K2D_FIX));
+                        facc[s][c3] = 0.0;
                     }
                 }
             };
@@ -579,9 +578,9 @@ __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
                 for (int c3 = 0; c3 < 3; c3++) d[c3] = min_image_d(S.xa[c3][a] - S.x[c3][k], A.box.L[c3], A.box.invL[c3]);
                 const double r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
                 const bool hit = valid && r2 < A.rc2;
-                float f[3][3];
+                double f[3][3];
 #pragma unroll
-                for (int s = 0; s < 3; s++) { f[s][0] = f[s][1] = f[s][2] = 0.0f; }
+                for (int s = 0; s < 3; s++) { f[s][0] = f[s][1] = f[s][2] = 0.0; }
                 if (hit) {
                     const double sig = 0.5 * (S.asig[a] + jsig), eps = S.aeps[a] * jeps, qq = S.aq[a] * jq;   // (eps: both are square roots)
                     double fc = 0.0;
@@ -593,8 +592,8 @@ __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
                     for (int s = 0; s < 3; s++) {
                         e[1 + s] += es[s];
                         if (!slot_on(s)) continue;
-                        const float ft = (float)(fs3[s] + A.le[s] * fc);
-                        f[s][0] = ft * (float)d[0]; f[s][1] = ft * (float)d[1]; f[s][2] = ft * (float)d[2];
+                        const double ft = fs3[s] + A.le[s] * fc;
+                        f[s][0] = ft * d[0]; f[s][1] = ft * d[1]; f[s][2] = ft * d[2];
                     }
                 }
                 // force on the item's alchemical atom: into the lane's running sums (flushed when the atom changes)
@@ -611,7 +610,7 @@ __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
                     for (int s = 0; s < 3; s++) {
                         if (!slot_on(s)) continue;
 #pragma unroll
-                        for (int c3 = 0; c3 < 3; c3++) atomicAdd(&S.fj[s * 3 + c3][ms], (unsigned long long)__double2ll_rn(-(double)f[s][c3] * K2D_FIX));
+                        for (int c3 = 0; c3 < 3; c3++) atomicAdd(&S.fj[s * 3 + c3][ms], (unsigned long long)__double2ll_rn(-f[s][c3] * K2D_FIX));
                     }
                 }
             }

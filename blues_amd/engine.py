@@ -235,6 +235,14 @@ class NativeEngine:
                 "nonbonded_kernel": s[12], "tiles_per_list": s[13], "atom_list_entries": s[14], "atom_list_iterations": s[15],
                 "atom_prunes": s[16], "pruned_list_entries": s[17], "pruned_list_iterations": s[18], "pruned_lists": s[19], "alchemical_kernel": s[20], "step_threads": s[21]}
 
+    def alchemical_layout(self):
+        """(PA, k2_jiter, entries of the alchemical j-list at the last build, entries of the alchemical exception rows): the shape the
+        alchemical kernels run in (include/blues_engine.h: blues_get_alchemical_layout); None from a library without the entry."""
+        if not hasattr(self._lib, "blues_get_alchemical_layout"):
+            return None
+        out = (C.c_int64 * 4)(); self._check(self._lib.blues_get_alchemical_layout(self._h, out))
+        return tuple(int(v) for v in out)
+
     def cmap_angles(self):
         """(phi, psi) of every CMAP torsion at the current device positions: (m, 2) radians in [0, 2 pi)."""
         m = len(np.asarray(self.system.cmap_torsions).reshape(-1, 9))

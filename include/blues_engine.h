@@ -447,6 +447,13 @@ int blues_get_exact_pme_path(BluesEngine *h, int64_t out[2]);
  * The static launch of the frozen charges is not counted.  Zeros without reciprocal space.  blues_get_global("pme_fast_launches") and
  * ("pme_general_launches") give one word each.  Additive (BLUES_ABI_VERSION unchanged). */
 int blues_get_pme_path(BluesEngine *h, int64_t out[2]);
+/* the shape the alchemical kernels run in, read from the host's layout (no launch): [0] PA, the alchemical region's size padded to a
+ * power of two (the lane layout is (j-slot, a) with 256 / PA j-slots per block) [1] k2_jiter, the j-groups an environment block
+ * walks, after its clamp to PA (1 << 20 under the dense form: one logical block) [2] entries of the alchemical atoms' j-list at the
+ * last list build (NoCutoff: every environment atom; 0 before the first build) [3] entries of the alchemical exception rows (a pair
+ * with both atoms alchemical has two, a pair with one has one).  Zeros for an engine without alchemical atoms.  Additive
+ * (BLUES_ABI_VERSION unchanged). */
+int blues_get_alchemical_layout(BluesEngine *h, int64_t out[4]);
 /* time `reps` launches of the dominant nonbonded kernel alone with HIP events
  * on the engine's own stream; returns mean microseconds per launch. */
 int blues_time_nonbonded(BluesEngine *h, int32_t reps, double *usec_per_launch);
