@@ -91,6 +91,12 @@ class BluesSystemExtV3(C.Structure):
                                           ("n_impropers", C.c_int32), ("improper_atoms", _ip), ("improper_params", _dp)]
 
 
+class BluesSystemExtV4(C.Structure):
+    """include/blues_engine.h: BluesSystemExtV4 (BluesSystemExtV3 grown at its end by the Lennard-Jones switch distance; passed in
+    BluesSystemExt's place with struct_size = its own size)."""
+    _fields_ = BluesSystemExtV3._fields_ + [("lj_switch_distance", C.c_double), ("lj_switch_reserved", C.c_double)]
+
+
 SYSTEM_EXT_SIZE_V1 = 8                     # a caller from before the CMAP fields: struct_size, alchemical_pme_treatment
 SYSTEM_EXT_SIZE_V2 = C.sizeof(BluesSystemExt)   # BLUES_SYSTEM_EXT_SIZE_V2: a caller with maps but no Urey-Bradley terms or impropers
 CMAP_MIN_SIZE, CMAP_MAX_SIZE = 4, 64       # BLUES_CMAP_MIN_SIZE / BLUES_CMAP_MAX_SIZE
@@ -131,7 +137,7 @@ class BluesMinimizeResult(C.Structure):
 MINIMIZE_FIELDS = ("dt0", "dt_max", "f_inc", "f_dec", "alpha0", "f_alpha", "max_step", "n_min")
 # additive entry points (BLUES_ABI_VERSION unchanged): a library built before them loads, and the wrappers that need them say so
 MINIMIZE_SYMBOLS = ("blues_minimize_default", "blues_minimize", "blues_batch_minimize")
-OPTIONAL_SYMBOLS = MINIMIZE_SYMBOLS + ("blues_engine_create_ext", "blues_get_exact_pme_path", "blues_get_pme_path", "blues_get_alchemical_layout", "blues_get_cmap_angles")
+OPTIONAL_SYMBOLS = MINIMIZE_SYMBOLS + ("blues_engine_create_ext", "blues_get_exact_pme_path", "blues_get_pme_path", "blues_get_alchemical_layout", "blues_get_cmap_angles", "blues_get_lj_switch")
 
 
 class BluesTuning(C.Structure):
@@ -241,6 +247,9 @@ class SystemData:
     urey_bradley_params: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))   # (n, 2): r0 nm, k kJ/mol/nm^2
     improper_atoms: np.ndarray = field(default_factory=lambda: np.zeros((0, 4), np.int32))
     improper_params: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))       # (n, 2): psi0 rad, k kJ/mol/rad^2
+    # createSystem's switchDistance, nm: the Lennard-Jones switching function of a periodic System between this distance and the cutoff
+    # (BluesSystemExtV4).  0, or a value >= the cutoff: no switch; on a NoCutoff System it is stored and has no effect, like the box
+    switch_distance: float = 0.0
 
     def __post_init__(self):
         alchemical_pme_treatment_code(self.alchemical_pme_treatment)
@@ -267,6 +276,19 @@ class SystemData:
             raise ValueError("alchemical_pme_treatment 'exact' with a switching_mode integrator is not supported: its force and energy "
                              "bookkeeping does not know the exact treatment's terms")
 
+    def check_switch_distance(self):
+        """What blues_engine_create_ext refuses about the switch distance, raised before a library is loaded (ValueError)."""
+        d = float(self.switch_distance)
+        if not np.isfinite(d) or d < 0.0:
+            raise ValueError("switch_distance %r: the switch distance of the Lennard-Jones switching function must be finite and not negative "
+                             "(0: no switch)" % (self.switch_distance,))
+
+    @property
+    def lj_switch_in_force(self):
+        """The switch distance the pair kernels apply: switch_distance on a periodic System where 0 < switch_distance < cutoff, else 0."""
+        d = float(self.switch_distance)
+        return d if int(self.nonbonded_method) != NB_NOCUTOFF and 0.0 < d < float(self.cutoff) else 0.0
+
     @property
     def has_cmap(self):
         return len(tuple(self.cmap_maps or ())) > 0 or np.asarray(self.cmap_torsions).size > 0
@@ -276,14 +298,19 @@ class SystemData:
         return np.asarray(self.urey_bradley_atoms).size > 0 or np.asarray(self.improper_atoms).size > 0
 
     def ext_desc(self):
-        """BluesSystemExt of this System -- BluesSystemExtV3 where it carries Urey-Bradley terms or impropers --, or None where
+        """BluesSystemExt of this System -- BluesSystemExtV3 where it carries Urey-Bradley terms or impropers, BluesSystemExtV4 where a
+        Lennard-Jones switch is in force (and only then: every other System passes the descriptor it always has) --, or None where
         blues_engine_create / blues_engine_create_gb say everything.  The numpy buffers of the maps and of the CHARMM terms stay alive
         with the descriptor (its _keep)."""
         code = alchemical_pme_treatment_code(self.alchemical_pme_treatment)
-        if code == 0 and not self.has_cmap and not self.has_charmm:
+        self.check_switch_distance()
+        switch = self.lj_switch_in_force
+        if code == 0 and not self.has_cmap and not self.has_charmm and switch == 0.0:
             return None
-        d = BluesSystemExtV3() if self.has_charmm else BluesSystemExt()
+        d = BluesSystemExtV4() if switch != 0.0 else (BluesSystemExtV3() if self.has_charmm else BluesSystemExt())
         d.struct_size = C.sizeof(d); d.alchemical_pme_treatment = code
+        if switch != 0.0:
+            d.lj_switch_distance = switch
         if self.has_cmap:
             maps = [_f64(m) for m in self.cmap_maps]
             tors = _i32(self.cmap_torsions, (-1, 9))
@@ -522,7 +549,7 @@ def declare_engine_prototypes(lib):
     protos = {
         "blues_engine_create": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.c_int, C.POINTER(H)], C.c_int),
         "blues_engine_create_gb": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_int, C.POINTER(H)], C.c_int),
-        "blues_engine_create_ext": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_void_p, C.c_int, C.POINTER(H)], C.c_int),   # (ext: BluesSystemExt or BluesSystemExtV3, told apart by struct_size)
+        "blues_engine_create_ext": ([C.POINTER(BluesSystemDesc), C.POINTER(BluesIntegratorDesc), C.POINTER(BluesImplicitSolventDesc), C.c_void_p, C.c_int, C.POINTER(H)], C.c_int),   # (ext: BluesSystemExt, BluesSystemExtV3 or BluesSystemExtV4, told apart by struct_size)
         "blues_engine_destroy": ([H], C.c_int),
         "blues_last_error": ([H], C.c_char_p),
         "blues_abi_version": ([], C.c_int),
@@ -549,6 +576,7 @@ def declare_engine_prototypes(lib):
         "blues_get_stats": ([H, C.POINTER(C.c_int64)], C.c_int),
         "blues_get_exact_pme_path": ([H, C.POINTER(C.c_int64)], C.c_int),
         "blues_get_pme_path": ([H, C.POINTER(C.c_int64)], C.c_int),
+        "blues_get_lj_switch": ([H, _dp], C.c_int),
         "blues_get_alchemical_layout": ([H, C.POINTER(C.c_int64)], C.c_int),
         "blues_get_cmap_angles": ([H, _dp], C.c_int),
         "blues_time_nonbonded": ([H, C.c_int32, _dp], C.c_int),
@@ -602,7 +630,7 @@ ENGINE_SYMBOLS = (
     "blues_set_positions", "blues_set_velocities", "blues_set_box", "blues_get_positions",
     "blues_get_velocities", "blues_get_forces", "blues_get_box", "blues_set_velocities_to_temperature",
     "blues_get_energy", "blues_get_energy_at", "blues_get_energy_terms", "blues_mesh_energy", "blues_step", "blues_run_switch", "blues_get_global",
-    "blues_set_global", "blues_reset", "blues_get_stats", "blues_get_exact_pme_path", "blues_get_pme_path", "blues_get_alchemical_layout", "blues_get_cmap_angles", "blues_time_nonbonded", "blues_time_list_build", "blues_audit_lists",
+    "blues_set_global", "blues_reset", "blues_get_stats", "blues_get_exact_pme_path", "blues_get_pme_path", "blues_get_lj_switch", "blues_get_alchemical_layout", "blues_get_cmap_angles", "blues_time_nonbonded", "blues_time_list_build", "blues_audit_lists",
     "blues_snapshot_capture", "blues_snapshot_release", "blues_snapshot_read", "blues_set_positions_from_snapshot",
     "blues_set_velocities_from_snapshot", "blues_snapshot_read_atoms", "blues_set_positions_from_snapshot_edited",
     "blues_batch_create", "blues_batch_destroy", "blues_batch_last_error", "blues_batch_size", "blues_batch_step", "blues_batch_set_active", "blues_batch_prefetch_energies",

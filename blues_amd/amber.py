@@ -278,7 +278,7 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
                       rigid_water=True, hydrogen_mass=None, remove_cm_motion=True, alchemical_atoms=(),
                       tip3p_for_untyped_water=True, reciprocal_space=True, dispersion_correction=True, nonbonded_method="PME",
                       implicit_solvent=None, solute_dielectric=1.0, solvent_dielectric=78.5, implicit_solvent_kappa=None,
-                      implicit_solvent_salt_conc=None, alchemical_pme_treatment="direct-space"):
+                      implicit_solvent_salt_conc=None, alchemical_pme_treatment="direct-space", switch_distance=None):
     """Amber topology -> SystemData, following structure.createSystem's kwargs
     (reference examples/rotmove_cuda.yml:19-27: PME, 10 A cutoff, HBonds,
     rigidWater, removeCMMotion, hydrogenMass 3.024, ewaldErrorTolerance 0.005).
@@ -293,7 +293,10 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
     blues/simulation.py:139-219): GB-OBC with the ACE surface term on a NoCutoff System, radii from %FLAG RADII and scale factors
     from %FLAG SCREEN.  HCT, GBn, GBn2 and salt screening (kappa, a salt concentration) are not implemented and raise.
     alchemical_pme_treatment="direct-space" | "exact" (SystemFactory.generateAlchSystem(..., alchemical_pme_treatment=...), reference
-    blues/simulation.py:236, 274-284): how full PME treats the alchemical charges; "exact" needs reciprocal space.  'coulomb' raises."""
+    blues/simulation.py:236, 274-284): how full PME treats the alchemical charges; "exact" needs reciprocal space.  'coulomb' raises.
+    switch_distance (nm; createSystem(switchDistance=...), reference blues/simulation.py:157-161, blues/settings.py:155): the Lennard-Jones
+    switching function between it and the cutoff.  None, 0 or a value >= the cutoff: no switch; on a NoCutoff System it is stored and
+    has no effect.  Negative or not finite raises."""
     from ._abi import alchemical_pme_treatment_code
     alchemical_pme_treatment_code(alchemical_pme_treatment)
     if nonbonded_method not in ("PME", "NoCutoff"):
@@ -498,7 +501,9 @@ def system_from_amber(prm, positions, box, cutoff=1.0, ewald_error_tolerance=0.0
         remove_cm_motion=remove_cm_motion, positions=np.asarray(positions, dtype=np.float64),
         residue_of_atom=residue_of_atom, names=list(prm.get("ATOM_NAME", [])),
         implicit_solvent=gb, alchemical_pme_treatment=alchemical_pme_treatment,
+        switch_distance=0.0 if switch_distance is None else float(switch_distance),
     )
+    system.check_switch_distance()
     system.cmap_maps, system.cmap_torsions = cmap_from_prmtop(prm, natom)   # (CMAPTorsionForce of ff19SB / chamber topologies)
     system.check_cmap()
     if chamber:   # (HarmonicBondForce of the Urey-Bradley terms, CustomTorsionForce of the impropers)

@@ -48,6 +48,7 @@ static_assert(T_CMAP > T_CENT, "T_CMAP is an entry type only, past T_CENT");
 static_assert(T_UREY > T_CMAP && T_IMPR > T_UREY, "T_UREY and T_IMPR are entry types only, past T_CMAP");
 static_assert(sizeof(BluesSystemExt) == BLUES_SYSTEM_EXT_SIZE_V2 && offsetof(BluesSystemExtV3, n_urey_bradley) == BLUES_SYSTEM_EXT_SIZE_V2, "the CHARMM fields begin where BluesSystemExt ends");
 // BluesSystemExtV3 begins with BluesSystemExt's layout, field for field: the two cannot drift apart
+static_assert(offsetof(BluesSystemExtV4, lj_switch_distance) == sizeof(BluesSystemExtV3) && sizeof(BluesSystemExtV4) == sizeof(BluesSystemExtV3) + 16, "the switch fields begin where BluesSystemExtV3 ends");
 #define BLUES_EXT_SAME(f) static_assert(offsetof(BluesSystemExtV3, f) == offsetof(BluesSystemExt, f) && sizeof(((BluesSystemExtV3*)nullptr)->f) == sizeof(((BluesSystemExt*)nullptr)->f), "BluesSystemExtV3." #f " lies where BluesSystemExt has it")
 BLUES_EXT_SAME(struct_size); BLUES_EXT_SAME(alchemical_pme_treatment); BLUES_EXT_SAME(n_cmap_maps); BLUES_EXT_SAME(cmap_size); BLUES_EXT_SAME(cmap_energy); BLUES_EXT_SAME(n_cmap_torsions); BLUES_EXT_SAME(cmap_torsion_map); BLUES_EXT_SAME(cmap_torsion_atoms);
 #undef BLUES_EXT_SAME
@@ -392,6 +393,9 @@ struct BluesEngine {
     DBuf<double> d_pmex_pq, d_pmex_eq, d_fex, d_pmex_e; DBuf<int> d_pmex_path;   // (d_pmex_path: launches per mesh path, counted by the kernel)
     DBuf<PmeExArgs<float>> d_pmex_rec_f; DBuf<PmeExArgs<double>> d_pmex_rec_d; long long pmex_rec_epoch = -1;   // a lone engine's own record (launch_pme_exact)
     double e_ewald_const = 0.0, e_disp = 0.0;   // self term + neutralising background; dispersion correction (functions of the box)
+    // Lennard-Jones switching function: the distance in force (0: none -- NoCutoff, or a value <= 0 or >= cutoff), whether the
+    // pair kernels are launched in their SW = true instantiations (LAUNCH_SW), and how many such launches there have been (blues_get_lj_switch)
+    double lj_switch = 0.0; bool lj_sw = false; long long lj_sw_launches = 0;
     // bonded
     DBuf<int> d_row_atom, d_row_start, d_ent_type, d_ent_term, d_ent_role;
     DBuf<int> d_term_atoms[T_NTYPES]; DBuf<double> d_term_params[T_NTYPES];
@@ -1690,10 +1694,20 @@ template <typename R> static int launch_lists(BluesEngine* h, int force, int pha
     return 0;
 }
 
+// A pair kernel in the instantiation the engine's Lennard-Jones switch asks for: K<TA..., true> where it has one (counted for
+// blues_get_lj_switch), K<TA..., false> -- the kernel an engine without a switch has always run -- otherwise.  TA in parentheses.
+// The switch's constants are the kernel's last argument (device_common.h: LjSw); the unswitched instantiation does not read it.
+static LjSw make_ljsw(const BluesEngine* h) { LjSw s; s.rs = h->lj_sw ? h->lj_switch : 0.0; s.iw = h->lj_sw ? 1.0 / (h->cutoff - h->lj_switch) : 0.0; return s; }
+#define SW_UNPAREN(...) __VA_ARGS__
+#define LAUNCH_SW(h, K, TA, ...) do { if ((h)->lj_sw) { hipLaunchKernelGGL((K<SW_UNPAREN TA, true>), __VA_ARGS__, make_ljsw(h)); (h)->lj_sw_launches++; } \
+                                      else hipLaunchKernelGGL((K<SW_UNPAREN TA, false>), __VA_ARGS__, make_ljsw(h)); } while (0)
+#define SET_LDS_SW(h, K, TA, bytes) ((h)->lj_sw ? hipFuncSetAttribute(reinterpret_cast<const void*>(&K<SW_UNPAREN TA, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)) \
+                                                : hipFuncSetAttribute(reinterpret_cast<const void*>(&K<SW_UNPAREN TA, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
+
 template <typename R, bool ENERGY, int WPB> static void launch_nb_wpb(BluesEngine* h, const NbArgs<R>& a, const typename Img<R>::Atom* img) {
     const int blocks = std::max(1, h->n_itiles) * (h->waves_tile / WPB);
-    if (batch_lead(h)) hipLaunchKernelGGL((k_nonbonded_b<R, ENERGY, WPB>), dim3(blocks * h->batch->R()), dim3(WPB * 64), 0, h->cur, batch_reps_nb<R>(h->batch), blocks, h->batch->R());
-    else if (!batch_dry(h)) hipLaunchKernelGGL((k_nonbonded<R, ENERGY, WPB>), dim3(blocks), dim3(WPB * 64), 0, h->cur, a, make_nbconst<R>(h), img);
+    if (batch_lead(h)) LAUNCH_SW(h, k_nonbonded_b, (R, ENERGY, WPB), dim3(blocks * h->batch->R()), dim3(WPB * 64), 0, h->cur, batch_reps_nb<R>(h->batch), blocks, h->batch->R());
+    else if (!batch_dry(h)) LAUNCH_SW(h, k_nonbonded, (R, ENERGY, WPB), dim3(blocks), dim3(WPB * 64), 0, h->cur, a, make_nbconst<R>(h), img);
 }
 
 template <typename R> static NbArgs<R> make_nb_args(BluesEngine* h) {
@@ -1719,12 +1733,12 @@ template <typename R> static NbArgs<R> make_nb_args(BluesEngine* h) {
 template <bool ENERGY> static int launch_nb_atom(BluesEngine* h, const NbArgs<float>& a) {
     if (h->jcap > NB_JCAP_MAX) E_FAIL(h, "internal: list capacity %d beyond the per-atom-list kernel's LDS layout", h->jcap);
     const size_t lds = (size_t)NB_LQ_BYTES + (size_t)h->jcap * 16 + NB_LDS_TAIL + (size_t)8 * 64 * std::min(h->S, std::max(1, h->n_itiles));
-    static thread_local size_t lds_set[2][2] = {{0, 0}, {0, 0}};   // [batched][ENERGY]: largest dynamic-LDS size the kernel was opened for
+    static thread_local size_t lds_set_sw[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};   // [switched][batched][ENERGY]: largest dynamic-LDS size the kernel was opened for
+    auto& lds_set = lds_set_sw[h->lj_sw ? 1 : 0];
     const bool lead = batch_lead(h);
     if (batch_dry(h)) return 0;
     if (lds > lds_set[lead][ENERGY]) {
-        hipError_t e = lead ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nonbonded_atom_b<ENERGY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                            : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nonbonded_atom<ENERGY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = lead ? SET_LDS_SW(h, k_nonbonded_atom_b, (ENERGY), lds) : SET_LDS_SW(h, k_nonbonded_atom, (ENERGY), lds);
         if (e != hipSuccess) E_FAIL(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
         lds_set[lead][ENERGY] = lds;
     }
@@ -1732,9 +1746,9 @@ template <bool ENERGY> static int launch_nb_atom(BluesEngine* h, const NbArgs<fl
     const int nthr = h->tune.k1_threads > 0 ? std::min(1024, std::max(64, (h->tune.k1_threads / 64) * 64)) : 1024;
     if (lead) {
         BluesBatch::EvPair* tp = ENERGY ? nullptr : k1t_begin(h->batch, h->cur);
-        hipLaunchKernelGGL((k_nonbonded_atom_b<ENERGY>), dim3(nb * h->batch->R()), dim3(nthr), lds, h->cur, h->batch->d_nb_f.p, nb, h->batch->R());
+        LAUNCH_SW(h, k_nonbonded_atom_b, (ENERGY), dim3(nb * h->batch->R()), dim3(nthr), lds, h->cur, h->batch->d_nb_f.p, nb, h->batch->R());
         k1t_end(tp, h->cur);
-    } else hipLaunchKernelGGL((k_nonbonded_atom<ENERGY>), dim3(nb), dim3(nthr), lds, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
+    } else LAUNCH_SW(h, k_nonbonded_atom, (ENERGY), dim3(nb), dim3(nthr), lds, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
     return 0;
 }
 
@@ -1747,14 +1761,14 @@ template <bool ENERGY> static void launch_nb_sub(BluesEngine* h, const NbArgs<fl
         const RepNb<float>* reps = h->batch->d_nb_f.p;
         const int nb = (waves + 3) / 4, nrep = h->batch->R();
         const dim3 bgrid(nb * nrep);
-        if (h->k1_iw == 8) hipLaunchKernelGGL((k_nonbonded_sub_b<ENERGY, 8>), bgrid, block, 0, h->cur, reps, nb, nrep);
-        else if (h->k1_iw == 16) hipLaunchKernelGGL((k_nonbonded_sub_b<ENERGY, 16>), bgrid, block, 0, h->cur, reps, nb, nrep);
-        else hipLaunchKernelGGL((k_nonbonded_sub_b<ENERGY, 32>), bgrid, block, 0, h->cur, reps, nb, nrep);
+        if (h->k1_iw == 8) LAUNCH_SW(h, k_nonbonded_sub_b, (ENERGY, 8), bgrid, block, 0, h->cur, reps, nb, nrep);
+        else if (h->k1_iw == 16) LAUNCH_SW(h, k_nonbonded_sub_b, (ENERGY, 16), bgrid, block, 0, h->cur, reps, nb, nrep);
+        else LAUNCH_SW(h, k_nonbonded_sub_b, (ENERGY, 32), bgrid, block, 0, h->cur, reps, nb, nrep);
         return;
     }
-    if (h->k1_iw == 8) hipLaunchKernelGGL((k_nonbonded_sub<ENERGY, 8>), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
-    else if (h->k1_iw == 16) hipLaunchKernelGGL((k_nonbonded_sub<ENERGY, 16>), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
-    else hipLaunchKernelGGL((k_nonbonded_sub<ENERGY, 32>), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
+    if (h->k1_iw == 8) LAUNCH_SW(h, k_nonbonded_sub, (ENERGY, 8), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
+    else if (h->k1_iw == 16) LAUNCH_SW(h, k_nonbonded_sub, (ENERGY, 16), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
+    else LAUNCH_SW(h, k_nonbonded_sub, (ENERGY, 32), grid, block, 0, h->cur, a, make_nbconst<float>(h), h->d_img_f.p);
 }
 
 static NcArgs make_nc_args(BluesEngine* h) {
@@ -1820,11 +1834,11 @@ template <typename R, bool ENERGY> static int launch_nonbonded(BluesEngine* h) {
             if (!batch_dry(h)) {
                 if (batch_lead(h)) {
                     BluesBatch::EvPair* tp = ENERGY ? nullptr : k1t_begin(h->batch, h->cur);
-                    if (h->frag_rel) hipLaunchKernelGGL((k_nonbonded_frag_b<ENERGY, true>), dim3(h->frag_nwg * h->batch->R()), dim3(FR_THREADS), 0, h->cur, h->batch->d_nb_f.p, h->frag_nwg, h->batch->R());
-                    else hipLaunchKernelGGL((k_nonbonded_frag_b<ENERGY, false>), dim3(h->frag_nwg * h->batch->R()), dim3(FR_THREADS), 0, h->cur, h->batch->d_nb_f.p, h->frag_nwg, h->batch->R());
+                    if (h->frag_rel) LAUNCH_SW(h, k_nonbonded_frag_b, (ENERGY, true), dim3(h->frag_nwg * h->batch->R()), dim3(FR_THREADS), 0, h->cur, h->batch->d_nb_f.p, h->frag_nwg, h->batch->R());
+                    else LAUNCH_SW(h, k_nonbonded_frag_b, (ENERGY, false), dim3(h->frag_nwg * h->batch->R()), dim3(FR_THREADS), 0, h->cur, h->batch->d_nb_f.p, h->frag_nwg, h->batch->R());
                     k1t_end(tp, h->cur);
-                } else if (h->frag_rel) hipLaunchKernelGGL((k_nonbonded_frag<ENERGY, true>), dim3(h->frag_nwg), dim3(FR_THREADS), 0, h->cur, make_frag_args(h), make_nbconst<float>(h));
-                else hipLaunchKernelGGL((k_nonbonded_frag<ENERGY, false>), dim3(h->frag_nwg), dim3(FR_THREADS), 0, h->cur, make_frag_args(h), make_nbconst<float>(h));
+                } else if (h->frag_rel) LAUNCH_SW(h, k_nonbonded_frag, (ENERGY, true), dim3(h->frag_nwg), dim3(FR_THREADS), 0, h->cur, make_frag_args(h), make_nbconst<float>(h));
+                else LAUNCH_SW(h, k_nonbonded_frag, (ENERGY, false), dim3(h->frag_nwg), dim3(FR_THREADS), 0, h->cur, make_frag_args(h), make_nbconst<float>(h));
             }
             h->st_launches++;
             HIP_OK(h, hipGetLastError());
@@ -1880,11 +1894,11 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
         const bool lead = batch_lead(h);
         if (h->k2_f32 && !energy) {
             // the fp32 form (kernels_alch.h: alchemical_dense32_body): its LDS record depends on how many force slots the pass produces
-            static thread_local bool opened32[2] = {false, false};
+            static thread_local bool opened32_sw[2][2] = {{false, false}, {false, false}};   // [switched][batched]
+            auto& opened32 = opened32_sw[h->lj_sw ? 1 : 0];
             if (!opened32[lead]) {
                 hipError_t e = hipSuccess;
-#define OPEN32(M, NS) do { if (e == hipSuccess) e = lead ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_alchemical_dense32_b<M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K2FLds<NS>)) \
-                                                          : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_alchemical_dense32<M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K2FLds<NS>)); } while (0)
+#define OPEN32(M, NS) do { if (e == hipSuccess) e = lead ? SET_LDS_SW(h, k_alchemical_dense32_b, (M), sizeof(K2FLds<NS>)) : SET_LDS_SW(h, k_alchemical_dense32, (M), sizeof(K2FLds<NS>)); } while (0)
                 OPEN32(5, 2); OPEN32(2, 1); OPEN32(-1, 3);
 #undef OPEN32
                 if (e != hipSuccess) E_FAIL(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
@@ -1896,26 +1910,26 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
                 const AlchDyn D = make_alch_dyn(A);
                 // (part 5 / 6: the dense kernel only, for the members that do not / do rebuild their lists in this pass -- force_pass, fork mode 4)
                 const int* stale = part >= 5 ? h->batch->d_work.p : nullptr;
-#define DENSE32_B(M, NS) do { if (part != 3) hipLaunchKernelGGL((k_alchemical_dense32_b<M>), dim3(nrep), dim3(K2F_THREADS), sizeof(K2FLds<NS>), h->cur, h->batch->d_core.p, D, stale, part == 6 ? 1 : 0); \
-                              if (part < 4) hipLaunchKernelGGL((k_alchemical_b<true, M>), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep); } while (0)
+#define DENSE32_B(M, NS) do { if (part != 3) LAUNCH_SW(h, k_alchemical_dense32_b, (M), dim3(nrep), dim3(K2F_THREADS), sizeof(K2FLds<NS>), h->cur, h->batch->d_core.p, D, stale, part == 6 ? 1 : 0); \
+                              if (part < 4) LAUNCH_SW(h, k_alchemical_b, (true, M, 0), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep); } while (0)
                 if (slot_mask == 5) DENSE32_B(5, 2); else if (slot_mask == 2) DENSE32_B(2, 1); else DENSE32_B(-1, 3);
 #undef DENSE32_B
             } else {
-                if (slot_mask == 5) hipLaunchKernelGGL(k_alchemical_dense32<5>, dim3(1), dim3(K2F_THREADS), sizeof(K2FLds<2>), h->cur, A);
-                else if (slot_mask == 2) hipLaunchKernelGGL(k_alchemical_dense32<2>, dim3(1), dim3(K2F_THREADS), sizeof(K2FLds<1>), h->cur, A);
-                else hipLaunchKernelGGL(k_alchemical_dense32<-1>, dim3(1), dim3(K2F_THREADS), sizeof(K2FLds<3>), h->cur, A);
-                hipLaunchKernelGGL(k_alchemical<true>, dim3(1), dim3(256), 0, h->cur, A);
+                if (slot_mask == 5) LAUNCH_SW(h, k_alchemical_dense32, (5), dim3(1), dim3(K2F_THREADS), sizeof(K2FLds<2>), h->cur, A);
+                else if (slot_mask == 2) LAUNCH_SW(h, k_alchemical_dense32, (2), dim3(1), dim3(K2F_THREADS), sizeof(K2FLds<1>), h->cur, A);
+                else LAUNCH_SW(h, k_alchemical_dense32, (-1), dim3(1), dim3(K2F_THREADS), sizeof(K2FLds<3>), h->cur, A);
+                LAUNCH_SW(h, k_alchemical, (true, 0), dim3(1), dim3(256), 0, h->cur, A);
             }
             h->st_launches++;
             HIP_OK(h, hipGetLastError());
             return 0;
         }
-        static thread_local bool opened[2] = {false, false};
+        static thread_local bool opened_sw[2][2] = {{false, false}, {false, false}};   // [switched][batched]
+        auto& opened = opened_sw[h->lj_sw ? 1 : 0];
         const size_t lds = sizeof(K2DLds);
         if (!opened[lead]) {
             hipError_t e = hipSuccess;
-#define OPEN(M) do { if (e == hipSuccess) e = lead ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_alchemical_dense_b<M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) \
-                                                    : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_alchemical_dense<M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); } while (0)
+#define OPEN(M) do { if (e == hipSuccess) e = lead ? SET_LDS_SW(h, k_alchemical_dense_b, (M), lds) : SET_LDS_SW(h, k_alchemical_dense, (M), lds); } while (0)
             OPEN(5); OPEN(2); OPEN(-1);
 #undef OPEN
             if (e != hipSuccess) E_FAIL(h, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
@@ -1925,15 +1939,15 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
             const int nrep = h->batch->R();
             const AlchDyn D = make_alch_dyn(A);
             // (part 3: the alchemical x alchemical block only; part 4: the dense kernel only -- force_pass, fork mode 3)
-#define DENSE_B(M) do { if (part != 3) hipLaunchKernelGGL((k_alchemical_dense_b<M>), dim3(nrep), dim3(K2D_THREADS), lds, h->cur, h->batch->d_core.p, D); \
-                        if (part != 4) hipLaunchKernelGGL((k_alchemical_b<true, M>), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep); } while (0)
+#define DENSE_B(M) do { if (part != 3) LAUNCH_SW(h, k_alchemical_dense_b, (M), dim3(nrep), dim3(K2D_THREADS), lds, h->cur, h->batch->d_core.p, D); \
+                        if (part != 4) LAUNCH_SW(h, k_alchemical_b, (true, M, 0), dim3(nrep), dim3(256), 0, h->cur, h->batch->d_core.p, D, 1, nrep); } while (0)
             if (slot_mask == 5) DENSE_B(5); else if (slot_mask == 2) DENSE_B(2); else DENSE_B(-1);
 #undef DENSE_B
         } else {
-            if (slot_mask == 5) hipLaunchKernelGGL(k_alchemical_dense<5>, dim3(1), dim3(K2D_THREADS), lds, h->cur, A);
-            else if (slot_mask == 2) hipLaunchKernelGGL(k_alchemical_dense<2>, dim3(1), dim3(K2D_THREADS), lds, h->cur, A);
-            else hipLaunchKernelGGL(k_alchemical_dense<-1>, dim3(1), dim3(K2D_THREADS), lds, h->cur, A);
-            hipLaunchKernelGGL(k_alchemical<true>, dim3(1), dim3(256), 0, h->cur, A);
+            if (slot_mask == 5) LAUNCH_SW(h, k_alchemical_dense, (5), dim3(1), dim3(K2D_THREADS), lds, h->cur, A);
+            else if (slot_mask == 2) LAUNCH_SW(h, k_alchemical_dense, (2), dim3(1), dim3(K2D_THREADS), lds, h->cur, A);
+            else LAUNCH_SW(h, k_alchemical_dense, (-1), dim3(1), dim3(K2D_THREADS), lds, h->cur, A);
+            LAUNCH_SW(h, k_alchemical, (true, 0), dim3(1), dim3(256), 0, h->cur, A);
         }
         h->st_launches++;
         HIP_OK(h, hipGetLastError());
@@ -1944,7 +1958,7 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
         const AlchDyn D = make_alch_dyn(A);
         const dim3 g(nb * nrep), b(256);
         if (h->pair_mode == BLUES_PAIR_ETHYLENE) {
-#define ALCH_B1(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M, 1>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep)
+#define ALCH_B1(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M, 1>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep, make_ljsw(h))   // (a NoCutoff form: never switched)
             if (fast) { if (slot_mask == 5) ALCH_B1(true, 5); else if (slot_mask == 2) ALCH_B1(true, 2); else ALCH_B1(true, -1); }
             else { if (slot_mask == 5) ALCH_B1(false, 5); else if (slot_mask == 2) ALCH_B1(false, 2); else ALCH_B1(false, -1); }
 #undef ALCH_B1
@@ -1952,17 +1966,17 @@ static int launch_alchemical(BluesEngine* h, const double ls[3], const double le
             HIP_OK(h, hipGetLastError());
             return 0;
         }
-#define ALCH_B(F, M) hipLaunchKernelGGL((k_alchemical_b<F, M>), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep)
+#define ALCH_B(F, M) LAUNCH_SW(h, k_alchemical_b, (F, M, 0), g, b, 0, h->cur, h->batch->d_core.p, D, nb, nrep)
         if (fast) { if (slot_mask == 5) ALCH_B(true, 5); else if (slot_mask == 2) ALCH_B(true, 2); else ALCH_B(true, -1); }
         else { if (slot_mask == 5) ALCH_B(false, 5); else if (slot_mask == 2) ALCH_B(false, 2); else ALCH_B(false, -1); }
 #undef ALCH_B
     } else if (!batch_dry(h)) {
         if (h->pair_mode == BLUES_PAIR_ETHYLENE) {
-            if (fast) hipLaunchKernelGGL((k_alchemical<true, 1>), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
-            else hipLaunchKernelGGL((k_alchemical<false, 1>), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
+            if (fast) hipLaunchKernelGGL((k_alchemical<true, 1>), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A, make_ljsw(h));
+            else hipLaunchKernelGGL((k_alchemical<false, 1>), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A, make_ljsw(h));
         }
-        else if (fast) hipLaunchKernelGGL(k_alchemical<true>, dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
-        else hipLaunchKernelGGL(k_alchemical<false>, dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
+        else if (fast) LAUNCH_SW(h, k_alchemical, (true, 0), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
+        else LAUNCH_SW(h, k_alchemical, (false, 0), dim3(h->k2_nblocks_env + 1), dim3(256), 0, h->cur, A);
     }
     h->st_launches++;
     HIP_OK(h, hipGetLastError());
@@ -2093,8 +2107,8 @@ template <typename R> static int launch_forces_fused(BluesEngine* h, const doubl
     const int nb3 = B.n_entry_blocks + ((int)h->mobile.size() * h->n_noise + 255) / 256;
     h->noise_draw_base = h->h_draw; h->noise_valid = true;
     BondedDyn BD; BD.draw_base = B.draw_base; BD.n_entry_blocks = B.n_entry_blocks;
-    if (batch_lead(h)) hipLaunchKernelGGL(k_forces_fused_b<R>, dim3(nb1 + nb2 + nb3, h->batch->R()), dim3(256), 0, h->cur, batch_reps_nb<R>(h->batch), h->batch->d_core.p, make_alch_dyn(A), BD, nb1, nb2);
-    else if (!batch_dry(h)) hipLaunchKernelGGL(k_forces_fused<R>, dim3(nb1 + nb2 + nb3), dim3(256), 0, h->cur, a, make_nbconst<R>(h), img, A, B, nb1, nb2);
+    if (batch_lead(h)) LAUNCH_SW(h, k_forces_fused_b, (R), dim3(nb1 + nb2 + nb3, h->batch->R()), dim3(256), 0, h->cur, batch_reps_nb<R>(h->batch), h->batch->d_core.p, make_alch_dyn(A), BD, nb1, nb2);
+    else if (!batch_dry(h)) LAUNCH_SW(h, k_forces_fused, (R), dim3(nb1 + nb2 + nb3), dim3(256), 0, h->cur, a, make_nbconst<R>(h), img, A, B, nb1, nb2);
     h->st_launches++;
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -2117,6 +2131,31 @@ static void pme_splines_host(double dr, int order, double* w) {
     w[order - 1] = div * dr * w[order - 2];
     for (int k = 1; k < order - 1; k++) w[order - k - 1] = div * ((dr + k) * w[order - k - 2] + (order - k - dr) * w[order - k - 1]);
     w[0] = div * (1.0 - dr) * w[0];
+}
+
+// I12 = int_rs^rc r^-10 (1 - S(r)) dr and I6 = int_rs^rc r^-4 (1 - S(r)) dr, S the switching function of device_common.h: a fixed
+// 32-point Gauss-Legendre rule (nodes by Newton iteration on P_32).  The integrands are polynomials in x times r^-10 / r^-4 on an interval
+// with rc / rs < 2 or so: the rule is exact to rounding (tests/test_lj_switch_cpu.py holds it to 1e-10 of an adaptive quadrature).
+static void lj_switch_shell_integrals(double rs, double rc, double* i12, double* i6) {
+    const int N = 32;
+    const double half = 0.5 * (rc - rs), mid = 0.5 * (rc + rs);
+    double a12 = 0.0, a6 = 0.0;
+    for (int i = 0; i < N; i++) {
+        double t = std::cos(M_PI * (i + 0.75) / (N + 0.5)), dp = 1.0;
+        for (int it = 0; it < 100; it++) {
+            double p0 = 1.0, p1 = t;
+            for (int k = 2; k <= N; k++) { const double p2 = ((2.0 * k - 1.0) * t * p1 - (k - 1.0) * p0) / k; p0 = p1; p1 = p2; }
+            dp = N * (t * p1 - p0) / (t * t - 1.0);
+            const double dt = p1 / dp;
+            t -= dt;
+            if (std::fabs(dt) < 1e-16) break;
+        }
+        const double w = 2.0 / ((1.0 - t * t) * dp * dp);
+        const double r = mid + half * t, x = (r - rs) / (rc - rs), oms = x * x * x * (10.0 + x * (-15.0 + 6.0 * x));   // 1 - S
+        const double r2 = r * r, r4 = r2 * r2;
+        a6 += w * oms / r4; a12 += w * oms / (r4 * r4 * r2);
+    }
+    *i12 = half * a12; *i6 = half * a6;
 }
 
 template <typename T> static int pme_tables(BluesEngine* h) {
@@ -2181,7 +2220,11 @@ template <typename T> static int pme_tables(BluesEngine* h) {
             s12 += cnt * e * s6_ * s6_; s6 += cnt * e * s6_;
         }
         const double tot = 0.5 * h->n * (h->n + 1.0), rc = h->cutoff, rc3 = rc * rc * rc, rc9 = rc3 * rc3 * rc3;
-        h->e_disp = 8.0 * h->n * (double)h->n * M_PI * (s12 / tot / (9.0 * rc9) - s6 / tot / (3.0 * rc3)) / V;
+        // with a switching function the pairs inside the shell rs < r < rc keep U S: the correction gains the integral of r^2 U (1 - S)
+        // over it, i.e. sigma^12 I12 - sigma^6 I6 per class with the same weights [recalled: the same function, with switch]
+        double i12 = 0.0, i6 = 0.0;
+        if (h->lj_sw) lj_switch_shell_integrals(h->lj_switch, rc, &i12, &i6);
+        h->e_disp = 8.0 * h->n * (double)h->n * M_PI * (s12 / tot * (1.0 / (9.0 * rc9) + i12) - s6 / tot * (1.0 / (3.0 * rc3) + i6)) / V;
     }
     h->pme_static_valid = false;
     return 0;
@@ -2731,7 +2774,7 @@ static int energy_terms(BluesEngine* h, double T[BLUES_N_ENERGY_TERMS]) {
         by_precision(h->precision, [&](auto tag) {
             using T = decltype(tag);
             hipLaunchKernelGGL(k_frozen_boxes<T>, dim3((g.nfb + 3) / 4), dim3(256), 0, h->stream, h->n, make_nbconst<T>(h), engine_img<T>(h), ep);
-            hipLaunchKernelGGL(k_energy_frozen<T>, dim3(g.nfb), dim3(256), 0, h->stream, h->n, make_nbconst<T>(h), engine_img<T>(h), h->d_ex_start.p, h->d_ex_idx.p, ep);
+            LAUNCH_SW(h, k_energy_frozen, (T), dim3(g.nfb), dim3(256), 0, h->stream, h->n, make_nbconst<T>(h), engine_img<T>(h), h->d_ex_start.p, h->d_ex_idx.p, ep);
         });
         h->st_launches += 2;
     }
@@ -3113,7 +3156,7 @@ static bool batch_congruent(const BluesEngine* a, const BluesEngine* b, const ch
     BC(n_itiles) BC(n_tiles) BC(jcap) BC(n_islots) BC(pool_cap) BC(PA) BC(k2_nblocks_env) BC(k2_jiter) BC(seg_len) BC(waves_tile) BC(wpb) BC(npart)
     BC(fuse_forces) BC(fast_step) BC(k2_dense) BC(k2_f32) BC(k1_iw) BC(k1_mode) BC(acap) BC(S) BC(n_lists) BC(n_entries) BC(int_blocks) BC(int_threads) BC(clusters_packed) BC(n_noise) BC(n_rows)
     BC(frag_F) BC(frag_NI) BC(frag_nblk) BC(frag_fpw) BC(frag_nwg) BC(frag_rel)
-    BC(cutoff) BC(alpha) BC(sc_alpha) BC(annih_elec) BC(annih_ster) BC(nb_method) BC(pme) BC(pme_K[0]) BC(pme_K[1]) BC(pme_K[2]) BC(pme_order) BC(restr_k) BC(total_mass)
+    BC(cutoff) BC(lj_switch) BC(alpha) BC(sc_alpha) BC(annih_elec) BC(annih_ster) BC(nb_method) BC(pme) BC(pme_K[0]) BC(pme_K[1]) BC(pme_K[2]) BC(pme_order) BC(restr_k) BC(total_mass)
     // (not the box: a MonteCarloBarostat leaves every member in its own; margins, fixed-point scales and PME tables are per member in the records)
 #undef BC
     if (a->clusters.size() != b->clusters.size()) { *why = "constraint clusters"; return false; }
@@ -3240,7 +3283,7 @@ static bool prefetch_frozen(BluesBatch* B, BluesEngine* lead, std::vector<char>&
         by_precision(lead->precision, [&](auto tag) {
             using T = decltype(tag);
             hipLaunchKernelGGL(k_frozen_boxes_b<T>, dim3((g.nfb + 3) / 4, count), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, (int)g.off_frozen);
-            hipLaunchKernelGGL(k_energy_frozen_b<T>, dim3(g.nfb, count), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, (int)g.off_frozen);
+            LAUNCH_SW(lead, k_energy_frozen_b, (T), dim3(g.nfb, count), dim3(256), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, (int)g.off_frozen);
             hipLaunchKernelGGL(k_sum_frozen_b<T>, dim3((count + 63) / 64), dim3(64), 0, B->stream, batch_reps_nb<T>(B), B->d_frozen_work.p, count, (int)g.off_frozen, g.nfb, B->d_frozen_sum.p);
         });
         if (hipStreamSynchronize(B->stream) != hipSuccess) throw std::string("frozen-frozen energy launch failed");
@@ -3650,7 +3693,7 @@ static void cmap_tables(HostTopology& T) {
 
 static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesIntegratorDesc* it, const BluesImplicitSolventDesc* gb, const BluesSystemExt* ext) {
     if (ext) {   // alchemical_pme_treatment: what the exact treatment refuses, each with its reason
-        if (ext->struct_size != (int32_t)sizeof(BluesSystemExtV3) && ext->struct_size != (int32_t)sizeof(BluesSystemExt) && ext->struct_size != BLUES_SYSTEM_EXT_SIZE_V1) E_FAIL(h, "BluesSystemExt: struct_size %d matches none of this library's %d (BluesSystemExtV3), %d (BluesSystemExt: maps, no CHARMM terms) and %d (a caller from before the CMAP fields)", ext->struct_size, (int)sizeof(BluesSystemExtV3), (int)sizeof(BluesSystemExt), BLUES_SYSTEM_EXT_SIZE_V1);
+        if (ext->struct_size != (int32_t)sizeof(BluesSystemExtV4) && ext->struct_size != (int32_t)sizeof(BluesSystemExtV3) && ext->struct_size != (int32_t)sizeof(BluesSystemExt) && ext->struct_size != BLUES_SYSTEM_EXT_SIZE_V1) E_FAIL(h, "BluesSystemExt: struct_size %d matches none of this library's %d (BluesSystemExtV4: a Lennard-Jones switch), %d (BluesSystemExtV3), %d (BluesSystemExt: maps, no CHARMM terms) and %d (a caller from before the CMAP fields)", ext->struct_size, (int)sizeof(BluesSystemExtV4), (int)sizeof(BluesSystemExtV3), (int)sizeof(BluesSystemExt), BLUES_SYSTEM_EXT_SIZE_V1);
         const int tr = ext->alchemical_pme_treatment;
         if (tr != BLUES_ALCH_PME_DIRECT_SPACE && tr != BLUES_ALCH_PME_EXACT) E_FAIL(h, "alchemical_pme_treatment %d: the engine knows 0 ('direct-space') and 1 ('exact')", tr);
         if (tr == BLUES_ALCH_PME_EXACT) {
@@ -3681,7 +3724,15 @@ static int create_impl(BluesEngine* h, const BluesSystemDesc* s, const BluesInte
         }
     }
     // CHARMM's Urey-Bradley terms and impropers (a caller of struct_size 8 or V2 has none): likewise
-    const BluesSystemExtV3* ext3 = ext && ext->struct_size == (int32_t)sizeof(BluesSystemExtV3) ? reinterpret_cast<const BluesSystemExtV3*>(ext) : nullptr;
+    const BluesSystemExtV3* ext3 = ext && ext->struct_size >= (int32_t)sizeof(BluesSystemExtV3) ? reinterpret_cast<const BluesSystemExtV3*>(ext) : nullptr;
+    // the Lennard-Jones switching function (a caller of an older struct_size has none): OpenMM's rule for "no switch" is a distance <= 0 or
+    // >= the cutoff [reference blues/settings.py, createSystem's switchDistance]; a NoCutoff System keeps the value and ignores it, like the box
+    const BluesSystemExtV4* ext4 = ext && ext->struct_size == (int32_t)sizeof(BluesSystemExtV4) ? reinterpret_cast<const BluesSystemExtV4*>(ext) : nullptr;
+    if (ext4) {
+        if (!std::isfinite(ext4->lj_switch_distance) || ext4->lj_switch_distance < 0.0) E_FAIL(h, "lj_switch_distance %g: the switch distance of the Lennard-Jones switching function must be finite and not negative (0: no switch)", ext4->lj_switch_distance);
+        if (ext4->lj_switch_reserved != 0.0) E_FAIL(h, "BluesSystemExtV4.lj_switch_reserved must be 0");
+        if (s->nonbonded_method != BLUES_NB_NOCUTOFF && ext4->lj_switch_distance > 0.0 && ext4->lj_switch_distance < s->cutoff) { h->lj_switch = ext4->lj_switch_distance; h->lj_sw = true; }
+    }
     const bool with_charmm = ext3 && (ext3->n_urey_bradley != 0 || ext3->n_impropers != 0);
     if (with_charmm) {
         if (ext3->n_urey_bradley < 0 || ext3->n_impropers < 0) E_FAIL(h, "CHARMM terms: %d Urey-Bradley terms and %d impropers", ext3->n_urey_bradley, ext3->n_impropers);
@@ -4718,6 +4769,12 @@ int blues_get_cmap_angles(BluesEngine* h, double* out) {
     return 0;
 }
 
+int blues_get_lj_switch(BluesEngine* h, double out[2]) {
+    if (!h || !out) return 1;
+    out[0] = h->lj_sw ? h->lj_switch : 0.0; out[1] = (double)h->lj_sw_launches;
+    return 0;
+}
+
 int blues_get_pme_path(BluesEngine* h, int64_t out[2]) {
     out[0] = out[1] = 0;
     if (!h->pme || !h->d_pme_path.p) return 0;
@@ -5086,6 +5143,7 @@ int blues_batch_create(BluesEngine* const* engines, int32_t count, BluesBatch** 
         if (engines[r]->switch_mode != BLUES_SWITCH_NONE) { g_batch_create_error = "the switching integrators (switching_mode != 0) step one engine at a time: their energy bookkeeping is synchronous"; return 2; }
         for (int q = 0; q < r; q++) if (engines[q] == engines[r]) { g_batch_create_error = "duplicate engine handle"; return 2; }
         if (nocut(engines[r]) != nocut(engines[0])) { g_batch_create_error = "a batch cannot mix NoCutoff (non-periodic) engines with periodic ones"; return 2; }
+        if (engines[r]->lj_switch != engines[0]->lj_switch) { g_batch_create_error = "a batch cannot mix members with different Lennard-Jones switch distances (or with and without a switch): its launches run one instantiation of the pair kernels"; return 2; }
         if ((engines[r]->gb_model != 0) != (engines[0]->gb_model != 0)) { g_batch_create_error = "a batch cannot mix members with and without implicit solvent"; return 2; }
         if (engines[r]->pair_mode != engines[0]->pair_mode || engines[r]->n_cent != engines[0]->n_cent) { g_batch_create_error = "a batch cannot mix engines with and without custom forces (custom pair form, centroid bonds)"; return 2; }
     }

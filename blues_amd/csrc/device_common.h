@@ -112,6 +112,36 @@ template <typename R> struct NbConst {
     EwaldPoly ew;      // mixed precision only
 };
 
+// Lennard-Jones switching function: the LAST argument of every kernel with a pair body, so that no argument record the
+// unswitched kernels read (NbConst, AlchArgs, a batch's RepNb / RepCore) changes its layout.  Only the SW = true instantiations of the
+// pair bodies load it; a batch shares one value (its members may not differ in it).  0 / 0 on an engine without a switch.
+struct LjSw { double rs, iw; };   // switch distance, 1 / (cutoff - switch distance)
+
+// The switching function of OpenMM's NonbondedForce [recalled]: x = (r - rs) / (rc - rs) clamped to [0, 1],
+//   S = 1 - 10 x^3 + 15 x^4 - 6 x^5,   S' = -30 x^2 (1 - x)^2 / (rc - rs).
+// Returns S - 1 (formed as x^3 (15 x - 6 x^2 - 10): no cancellation near rs) and *dS = S'.  The clamp instead of a branch: a lane inside rs
+// gets S - 1 = 0 and S' = 0 exactly, a wave does not diverge.  A pair's energy U becomes U S, its force scale fs S - U S' / r.
+template <typename R> __device__ __forceinline__ R lj_switch_m1(R r, R rs, R iw, R* dS) {
+    R x = (r - rs) * iw;
+    x = x < (R)0 ? (R)0 : (x > (R)1 ? (R)1 : x);
+    const R x2 = x * x, omx = (R)1 - x;
+    *dS = (R)-30 * x2 * omx * omx * iw;
+    return x2 * x * (x * ((R)15 - (R)6 * x) - (R)10);
+}
+template <> __device__ __forceinline__ float lj_switch_m1<float>(float r, float rs, float iw, float* dS) {
+    const float x = __builtin_amdgcn_fmed3f((r - rs) * iw, 0.0f, 1.0f);
+    const float x2 = x * x, omx = 1.0f - x;
+    *dS = -30.0f * x2 * omx * omx * iw;
+    return x2 * x * fmaf(x, fmaf(-6.0f, x, 15.0f), -10.0f);
+}
+// the same applied to an fp64 pair term (the alchemical kernels): U -> U S, fs -> fs S - U S' / r
+__device__ __forceinline__ void lj_switch_apply_d(double r2, double rs, double iw, double* U, double* fs) {
+    const double r = sqrt(r2);
+    double dS; const double sm1 = lj_switch_m1<double>(r, rs, iw, &dS);
+    *fs = *fs + *fs * sm1 - *U * dS / r;
+    *U = *U + *U * sm1;
+}
+
 // Regular (non-alchemical) pair: 12-6 LJ + erfc-screened Coulomb.  r2 < cutoff^2 is the caller's business.
 // q is pre-multiplied by sqrt(ONE_4PI_EPS0); sig = hs_i+hs_j; eps4 = se_i*se_j.
 // Returns fscale = -dU/dr / r ; *e_lj, *e_c energies (dead code in the callers that do not use them).
@@ -155,6 +185,28 @@ template <> __device__ inline double pair_regular<double>(double r2, double qq, 
     *e_c = qq * ec * inv_r;
     f += qq * (ec * inv_r + TWO_OVER_SQRT_PI * alpha * ex) * inv_r2;
     return f;
+}
+
+// The pair bodies' call: SW = false IS pair_regular<R> (the same expressions, nothing else); SW = true switches the 12-6 term (Coulomb is
+// not switched) -- it takes the 12-6 force scale and r apart again by pair_regular's own expressions, which the compiler folds into them.
+template <typename R, bool SW> __device__ __forceinline__ R pair_regular_s(R r2, R qq, R sig, R eps4, const NbConst<R>& c, const LjSw& sw, R* e_lj, R* e_c) {
+    const R fs = pair_regular<R>(r2, qq, sig, eps4, c, e_lj, e_c);
+    if constexpr (!SW) return fs;
+    else if constexpr (sizeof(R) == 4) {
+        const float inv_r = __builtin_amdgcn_rsqf(r2), inv_r2 = inv_r * inv_r;
+        const float s2 = sig * sig * inv_r2, s6 = s2 * s2 * s2, t = eps4 * s6;
+        const float flj = t * fmaf(12.0f, s6, -6.0f), u = t * (s6 - 1.0f);
+        float dS; const float sm1 = lj_switch_m1<float>(r2 * inv_r, (float)sw.rs, (float)sw.iw, &dS);
+        *e_lj = fmaf(u, sm1, u);
+        return fmaf(flj * inv_r2, sm1, fmaf(-u * dS, inv_r, fs));
+    } else {
+        const double r = sqrt(r2), inv_r = 1.0 / r, inv_r2 = inv_r * inv_r;
+        const double s2 = sig * sig * inv_r2, s6 = s2 * s2 * s2;
+        const double u = eps4 * (s6 * s6 - s6), flj = eps4 * (12.0 * s6 * s6 - 6.0 * s6) * inv_r2;
+        double dS; const double sm1 = lj_switch_m1<double>(r, sw.rs, sw.iw, &dS);
+        *e_lj = u + u * sm1;
+        return fs + flj * sm1 - u * dS * inv_r;
+    }
 }
 
 // fp64 forms used by the alchemical kernel.

@@ -79,8 +79,10 @@ __device__ inline bool excluded_sorted(const int* ex_start, const int* ex_idx, i
 // Energies fp64 in both precisions (they are the protocol work); the force scale and its components are fp64 too,
 // as in the env blocks of form 0.
 // Returns false when the (env) block had no list entries left, i.e. every later block is empty too.
-template <bool FAST, int MASK = -1, int FORM = 0>
-__device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id) {
+// SW: the Lennard-Jones switching function on the sterics of the alchemical x environment and alchemical x alchemical pairs (one S, S'
+// per pair serves the three slots); Coulomb and the exception rows are not switched.
+template <bool FAST, int MASK = -1, int FORM = 0, bool SW = false>
+__device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id, const LjSw& sw) {
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int PA = A.PA;
@@ -186,6 +188,12 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                         double es[3], fs3[3];
                         if (same_ls) { softcore_lj1_fast_d(r2, sig, eps, A.ls[0], A.sc_alpha, &es[0], &fs3[0]); es[1] = es[2] = es[0]; fs3[1] = fs3[2] = fs3[0]; }
                         else softcore_lj3_fast_d(r2, sig, eps, A.ls, A.sc_alpha, es, fs3);
+                        if constexpr (SW) {
+                            const double inv_r = rsqrt_fast_d(r2);
+                            double dS; const double sm1 = lj_switch_m1<double>(r2 * inv_r, sw.rs, sw.iw, &dS);
+#pragma unroll
+                            for (int s = 0; s < 3; s++) { fs3[s] = fs3[s] + fs3[s] * sm1 - es[s] * dS * inv_r; es[s] = es[s] + es[s] * sm1; }
+                        }
 #pragma unroll
                         for (int s = 0; s < 3; s++) {
                             e[1 + s] += es[s];
@@ -198,7 +206,9 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
 #pragma unroll
                         for (int s = 0; s < 3; s++) {
                             double fs;
-                            e[1 + s] += softcore_lj_d(r2, sig, eps, A.ls[s], A.sc_alpha, &fs);
+                            double us = softcore_lj_d(r2, sig, eps, A.ls[s], A.sc_alpha, &fs);
+                            if constexpr (SW) lj_switch_apply_d(r2, sw.rs, sw.iw, &us, &fs);
+                            e[1 + s] += us;
                             const double ft = fs + A.le[s] * fc;
                             f[s][0] = ft * d[0]; f[s][1] = ft * d[1]; f[s][2] = ft * d[2];
                         }
@@ -265,11 +275,19 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
                         double fc, fl = 0.0;
                         const double ec = coulomb_d(r2, A.charge[ao] * A.charge[bo], A.alpha, A.pme != 0, &fc);
                         if (A.annih_elec) e[0] += 0.5 * ec; else e[5] += 0.5 * ec;
-                        if (!A.annih_ster) e[4] += 0.5 * plain_lj_d(r2, sig, eps, &fl);
+                        if (!A.annih_ster) {
+                            double ul = plain_lj_d(r2, sig, eps, &fl);
+                            if constexpr (SW) { if (A.pme) lj_switch_apply_d(r2, sw.rs, sw.iw, &ul, &fl); }
+                            e[4] += 0.5 * ul;
+                        }
 #pragma unroll
                         for (int s = 0; s < 3; s++) {
                             double fs = fl;
-                            if (A.annih_ster) e[1 + s] += 0.5 * softcore_lj_d(r2, sig, eps, A.ls[s], A.sc_alpha, &fs);
+                            if (A.annih_ster) {
+                                double us = softcore_lj_d(r2, sig, eps, A.ls[s], A.sc_alpha, &fs);
+                                if constexpr (SW) { if (A.pme) lj_switch_apply_d(r2, sw.rs, sw.iw, &us, &fs); }
+                                e[1 + s] += 0.5 * us;
+                            }
                             const double ft = fs + (A.annih_elec ? A.le[s] : 1.0) * fc;
                             g[s][0] = ft * d[0]; g[s][1] = ft * d[1]; g[s][2] = ft * d[2];
                         }
@@ -380,11 +398,11 @@ __device__ __forceinline__ bool alchemical_body(AlchArgs& A, const int block_id)
 // not depend on nphys.  (Sized for the list's CAPACITY, 4 of 5 blocks of a launch were empty and each still held an
 // occupancy slot for three dependent loads.)
 #define K2_PHYS 24
-template <bool FAST, int MASK = -1, int FORM = 0>
-__device__ __forceinline__ void alchemical_blocks(AlchArgs& A, const int p, const int nphys) {
-    if (p >= nphys) { alchemical_body<FAST, MASK, FORM>(A, A.nblocks_env); return; }
+template <bool FAST, int MASK = -1, int FORM = 0, bool SW = false>
+__device__ __forceinline__ void alchemical_blocks(AlchArgs& A, const int p, const int nphys, const LjSw& sw) {
+    if (p >= nphys) { alchemical_body<FAST, MASK, FORM, SW>(A, A.nblocks_env, sw); return; }
     for (int lb = p; lb < A.nblocks_env; lb += nphys) {
-        if (!alchemical_body<FAST, MASK, FORM>(A, lb)) return;
+        if (!alchemical_body<FAST, MASK, FORM, SW>(A, lb, sw)) return;
         __syncthreads();   // the next logical block reuses the LDS staging and partial arrays
     }
 }
@@ -423,8 +441,8 @@ struct K2DLds {
 
 static_assert(sizeof(K2DLds) <= 160 * 1024, "the dense alchemical kernel's record must fit the LDS of a CU");
 
-template <int MASK>
-__device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
+template <int MASK, bool SW = false>
+__device__ __forceinline__ void alchemical_dense_body(AlchArgs& A, const LjSw& sw) {
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
     extern __shared__ __align__(16) unsigned char k2d_smem[];
     K2DLds& S = *reinterpret_cast<K2DLds*>(k2d_smem);
@@ -588,6 +606,12 @@ __device__ __forceinline__ void alchemical_dense_body(AlchArgs& A) {
                     double es[3], fs3[3];
                     if (same_ls) { softcore_lj1_fast_d(r2, sig, eps, A.ls[0], A.sc_alpha, &es[0], &fs3[0]); es[1] = es[2] = es[0]; fs3[1] = fs3[2] = fs3[0]; }
                     else softcore_lj3_fast_d(r2, sig, eps, A.ls, A.sc_alpha, es, fs3);
+                    if constexpr (SW) {
+                        const double inv_r = rsqrt_fast_d(r2);
+                        double dS; const double sm1 = lj_switch_m1<double>(r2 * inv_r, sw.rs, sw.iw, &dS);
+#pragma unroll
+                        for (int s = 0; s < 3; s++) { fs3[s] = fs3[s] + fs3[s] * sm1 - es[s] * dS * inv_r; es[s] = es[s] + es[s] * sm1; }
+                    }
 #pragma unroll
                     for (int s = 0; s < 3; s++) {
                         e[1 + s] += es[s];
@@ -693,8 +717,8 @@ template <int NS> struct K2FLds {
 };
 static_assert(sizeof(K2FLds<2>) <= 76 * 1024, "two workgroups of the fp32 dense alchemical kernel per CU, with room for the allocation granule");
 
-template <int MASK>
-__device__ __forceinline__ void alchemical_dense32_body(AlchArgs& A) {
+template <int MASK, bool SW = false>
+__device__ __forceinline__ void alchemical_dense32_body(AlchArgs& A, const LjSw& sw) {
     constexpr int NS = MASK == 5 ? 2 : (MASK == 2 ? 1 : 3);                    // force slots this instantiation produces
     auto slot_on = [&](int s) -> bool { return MASK >= 0 ? ((MASK >> s) & 1) != 0 : ((A.slot_mask >> s) & 1) != 0; };
     auto slot_ix = [&](int s) -> int { return MASK == 5 ? (s >> 1) : (MASK == 2 ? 0 : s); };   // where slot s lives among the NS accumulators
@@ -714,6 +738,8 @@ __device__ __forceinline__ void alchemical_dense32_body(AlchArgs& A) {
     const float dl01 = (float)(A.ls[1] - A.ls[0]), dl12 = (float)(A.ls[2] - A.ls[1]);
     const float rc2 = (float)A.rc2, alpha = (float)A.alpha, c2 = TWO_OVER_SQRT_PI_F * (float)A.alpha;
     const float sc0 = A.fscale[0], sc1 = A.fscale[1], sc2 = A.fscale[2];
+    float sw_rs = 0.0f, sw_iw = 0.0f;
+    if constexpr (SW) { sw_rs = (float)sw.rs; sw_iw = (float)sw.iw; }
     if (tid < 16) {
         const bool on = tid < A.n_alch;
         const AlchARec ar = A.arec[on ? tid : 0];
@@ -797,18 +823,39 @@ __device__ __forceinline__ void alchemical_dense32_body(AlchArgs& A) {
                         const float g6 = 6.0f * eps4 * q4 * inv_s2;
                         const float den0 = sA[0] + q6, x0 = __builtin_amdgcn_rcpf(den0);
                         const float u0 = x0 * x0 * (1.0f - den0);          // x (x - 1) without the cancellation at x ~ 1
-                        eS0 += (double)(ls[0] * eps4 * u0);
-                        fs[0] = ls[0] * g6 * fmaf(2.0f, x0, -1.0f) * x0 * x0;
-                        if (same_ls) { fs[1] = fs[2] = fs[0]; }
-                        else {
-                            const float den1 = sA[1] + q6, x1 = __builtin_amdgcn_rcpf(den1), den2 = sA[2] + q6, x2 = __builtin_amdgcn_rcpf(den2);
-                            const float u1 = x1 * x1 * (1.0f - den1);
-                            // (A_0 - A_1) = alpha (ls_1 - ls_0) = dA01; x_1 - x_0 = dA01 x_0 x_1
-                            const float d01 = dA01 * x0 * x1, d12 = dA12 * x1 * x2;
-                            eD01 += (double)(eps4 * fmaf(ls[1] * d01, x0 + x1 - 1.0f, dl01 * u0));
-                            eD12 += (double)(eps4 * fmaf(ls[2] * d12, x1 + x2 - 1.0f, dl12 * u1));
-                            fs[1] = ls[1] * g6 * fmaf(2.0f, x1, -1.0f) * x1 * x1;
-                            fs[2] = ls[2] * g6 * fmaf(2.0f, x2, -1.0f) * x2 * x2;
+                        if constexpr (!SW) {
+                            eS0 += (double)(ls[0] * eps4 * u0);
+                            fs[0] = ls[0] * g6 * fmaf(2.0f, x0, -1.0f) * x0 * x0;
+                            if (same_ls) { fs[1] = fs[2] = fs[0]; }
+                            else {
+                                const float den1 = sA[1] + q6, x1 = __builtin_amdgcn_rcpf(den1), den2 = sA[2] + q6, x2 = __builtin_amdgcn_rcpf(den2);
+                                const float u1 = x1 * x1 * (1.0f - den1);
+                                // (A_0 - A_1) = alpha (ls_1 - ls_0) = dA01; x_1 - x_0 = dA01 x_0 x_1
+                                const float d01 = dA01 * x0 * x1, d12 = dA12 * x1 * x2;
+                                eD01 += (double)(eps4 * fmaf(ls[1] * d01, x0 + x1 - 1.0f, dl01 * u0));
+                                eD12 += (double)(eps4 * fmaf(ls[2] * d12, x1 + x2 - 1.0f, dl12 * u1));
+                                fs[1] = ls[1] * g6 * fmaf(2.0f, x1, -1.0f) * x1 * x1;
+                                fs[2] = ls[2] * g6 * fmaf(2.0f, x2, -1.0f) * x2 * x2;
+                            }
+                        } else {
+                            // The same with the switching function.  S depends on r alone, so the energy of every slot AND the per-pair differences
+                            // D_01, D_12 take the one factor S (the work is still formed from small numbers); a slot's force is fs S - U_s S' / r
+                            // with U_s = ls_s eps4 x_s (x_s - 1)
+                            const float inv_r = __builtin_amdgcn_rsqf(r2);
+                            float dS; const float Sw = 1.0f + lj_switch_m1<float>(r2 * inv_r, sw_rs, sw_iw, &dS), dSr = dS * inv_r;
+                            const float e0 = ls[0] * eps4 * u0;
+                            eS0 += (double)(e0 * Sw);
+                            fs[0] = fmaf(ls[0] * g6 * fmaf(2.0f, x0, -1.0f) * x0 * x0, Sw, -e0 * dSr);
+                            if (same_ls) { fs[1] = fs[2] = fs[0]; }
+                            else {
+                                const float den1 = sA[1] + q6, x1 = __builtin_amdgcn_rcpf(den1), den2 = sA[2] + q6, x2 = __builtin_amdgcn_rcpf(den2);
+                                const float u1 = x1 * x1 * (1.0f - den1), u2 = x2 * x2 * (1.0f - den2);
+                                const float d01 = dA01 * x0 * x1, d12 = dA12 * x1 * x2;
+                                eD01 += (double)(eps4 * fmaf(ls[1] * d01, x0 + x1 - 1.0f, dl01 * u0) * Sw);
+                                eD12 += (double)(eps4 * fmaf(ls[2] * d12, x1 + x2 - 1.0f, dl12 * u1) * Sw);
+                                fs[1] = fmaf(ls[1] * g6 * fmaf(2.0f, x1, -1.0f) * x1 * x1, Sw, -(ls[1] * eps4 * u1) * dSr);
+                                fs[2] = fmaf(ls[2] * g6 * fmaf(2.0f, x2, -1.0f) * x2 * x2, Sw, -(ls[2] * eps4 * u2) * dSr);
+                            }
                         }
                     }
 #pragma unroll
@@ -890,11 +937,11 @@ __device__ __forceinline__ void alchemical_dense32_body(AlchArgs& A) {
     NB_STAMP(stamp_wg && tid == 0, 60);
 }
 
-template <int MASK>
-__global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32(AlchArgs A) { alchemical_dense32_body<MASK>(A); }
+template <int MASK, bool SW = false>
+__global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32(AlchArgs A, LjSw sw) { alchemical_dense32_body<MASK, SW>(A, sw); }
 
-template <int MASK>
-__global__ void __launch_bounds__(K2D_THREADS) k_alchemical_dense(AlchArgs A) { alchemical_dense_body<MASK>(A); }
+template <int MASK, bool SW = false>
+__global__ void __launch_bounds__(K2D_THREADS) k_alchemical_dense(AlchArgs A, LjSw sw) { alchemical_dense_body<MASK, SW>(A, sw); }
 
-template <bool FAST, int FORM = 0>
-__global__ void __launch_bounds__(256) k_alchemical(AlchArgs A) { alchemical_blocks<FAST, -1, FORM>(A, blockIdx.x, gridDim.x - 1); }
+template <bool FAST, int FORM = 0, bool SW = false>
+__global__ void __launch_bounds__(256) k_alchemical(AlchArgs A, LjSw sw) { alchemical_blocks<FAST, -1, FORM, SW>(A, blockIdx.x, gridDim.x - 1, sw); }

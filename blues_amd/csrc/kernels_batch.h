@@ -118,31 +118,31 @@ __global__ void __launch_bounds__(ATOM_LIST_THREADS) k_build_atom_lists_b(const 
     }
 }
 
-template <typename R, bool ENERGY, int WPB>
-__global__ void __launch_bounds__(WPB * 64) k_nonbonded_b(const RepNb<R>* __restrict__ reps, int nb, int nrep) {
+template <typename R, bool ENERGY, int WPB, bool SW = false>
+__global__ void __launch_bounds__(WPB * 64) k_nonbonded_b(const RepNb<R>* __restrict__ reps, int nb, int nrep, LjSw sw) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     const RepNb<R>& rp = reps[rep];
     if (!rp.active) return;
     const NbArgs<R> a = rp.nb; const NbConst<R> c = rp.c;
-    nonbonded_body<R, ENERGY, WPB>(a, c, rp.img, bx);
+    nonbonded_body<R, ENERGY, WPB, SW>(a, c, rp.img, bx, sw);
 }
 
-template <bool ENERGY, int IW>
-__global__ void __launch_bounds__(256) k_nonbonded_sub_b(const RepNb<float>* __restrict__ reps, int nb, int nrep) {
+template <bool ENERGY, int IW, bool SW = false>
+__global__ void __launch_bounds__(256) k_nonbonded_sub_b(const RepNb<float>* __restrict__ reps, int nb, int nrep, LjSw sw) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     const RepNb<float>& rp = reps[rep];
     if (!rp.active) return;
     const NbArgs<float> a = rp.nb; const NbConst<float> c = rp.c;
-    nonbonded_sub_body<ENERGY, IW>(a, c, rp.img, bx);
+    nonbonded_sub_body<ENERGY, IW, SW>(a, c, rp.img, bx, sw);
 }
 
-template <bool ENERGY>
-__global__ void __launch_bounds__(1024) k_nonbonded_atom_b(const RepNb<float>* __restrict__ reps, int nb, int nrep) {
+template <bool ENERGY, bool SW = false>
+__global__ void __launch_bounds__(1024) k_nonbonded_atom_b(const RepNb<float>* __restrict__ reps, int nb, int nrep, LjSw sw) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     const RepNb<float>& rp = reps[rep];
     if (!rp.active) return;
     const NbArgs<float> a = rp.nb; const NbConst<float> c = rp.c;
-    nonbonded_atom_body<ENERGY>(a, c, rp.img, bx);
+    nonbonded_atom_body<ENERGY, SW>(a, c, rp.img, bx, sw);
 }
 
 // ---- fragment lists (kernels_frag.h): every member's first kernel of a pass, the work list of the members whose lists need
@@ -196,13 +196,13 @@ __global__ void __launch_bounds__(FR_THREADS) k_frag_lists_b(const RepNb<float>*
         frag_lists_body(fa, force, i - m * bpc);
     }
 }
-template <bool ENERGY, bool REL>
-__global__ void __launch_bounds__(FR_THREADS, FR_MIN_WAVES) k_nonbonded_frag_b(const RepNb<float>* __restrict__ reps, int nb, int nrep) {
+template <bool ENERGY, bool REL, bool SW = false>
+__global__ void __launch_bounds__(FR_THREADS, FR_MIN_WAVES) k_nonbonded_frag_b(const RepNb<float>* __restrict__ reps, int nb, int nrep, LjSw sw) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     const RepNb<float>& rp = reps[rep];
     if (!rp.active) return;
     const FragArgs fa = rp.fr; const NbConst<float> c = rp.c;
-    nonbonded_frag_body<ENERGY, REL>(fa, c, bx);
+    nonbonded_frag_body<ENERGY, REL, SW>(fa, c, bx, sw);
 }
 
 // reciprocal space of every member: one workgroup each (kernels_pme.h)
@@ -228,34 +228,34 @@ __global__ void __launch_bounds__(256) k_gather_pme_e_b(const RepNb<R>* __restri
     if (r < nrep) out[r] = reps[r].active && reps[r].pme.epart ? reps[r].pme.epart[0] : 0.0;
 }
 
-template <bool FAST, int MASK, int FORM = 0>
-__global__ void __launch_bounds__(256, 3) k_alchemical_b(const RepCore* __restrict__ reps, AlchDyn d, int nb, int nrep) {
+template <bool FAST, int MASK, int FORM = 0, bool SW = false>
+__global__ void __launch_bounds__(256, 3) k_alchemical_b(const RepCore* __restrict__ reps, AlchDyn d, int nb, int nrep, LjSw sw) {
     int rep, bx; batch_decode(nb, nrep, rep, bx);
     if (!reps[rep].active) return;
     AlchArgs A = reps[rep].al; apply_dyn(A, d);
-    alchemical_blocks<FAST, MASK, FORM>(A, bx, nb - 1);
+    alchemical_blocks<FAST, MASK, FORM, SW>(A, bx, nb - 1, sw);
 }
 
 // dense form of the env pairs (kernels_alch.h: alchemical_dense_body): one workgroup per member
-template <int MASK>
-__global__ void __launch_bounds__(K2D_THREADS) k_alchemical_dense_b(const RepCore* __restrict__ reps, AlchDyn d) {
+template <int MASK, bool SW = false>
+__global__ void __launch_bounds__(K2D_THREADS) k_alchemical_dense_b(const RepCore* __restrict__ reps, AlchDyn d, LjSw sw) {
     const int rep = blockIdx.x;
     if (!reps[rep].active) return;
     AlchArgs A = reps[rep].al; apply_dyn(A, d);
-    alchemical_dense_body<MASK>(A);
+    alchemical_dense_body<MASK, SW>(A, sw);
 }
 
 // ... and its fp32 form (round 6, kernels_alch.h: alchemical_dense32_body): two workgroups per CU
 // stale / want (BluesTuning.fork = 4): null = every member; else the work list of the rebuild (k_gather_stale_b) and which side of
 // it this launch serves -- 0: the members that do not rebuild their lists in this pass (they need nothing from the rebuild and run
 // beside it), 1: those that do (behind the builder of the group lists, which leaves the alchemical tile's list)
-template <int MASK>
-__global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32_b(const RepCore* __restrict__ reps, AlchDyn d, const int* __restrict__ stale, int want) {
+template <int MASK, bool SW = false>
+__global__ void __launch_bounds__(K2F_THREADS, 4) k_alchemical_dense32_b(const RepCore* __restrict__ reps, AlchDyn d, const int* __restrict__ stale, int want, LjSw sw) {
     const int rep = blockIdx.x;
     if (!reps[rep].active) return;
     if (stale && stale[1 + gridDim.x + rep] != want) return;
     AlchArgs A = reps[rep].al; apply_dyn(A, d);
-    alchemical_dense32_body<MASK>(A);
+    alchemical_dense32_body<MASK, SW>(A, sw);
 }
 
 template <bool CENT = false, bool CMAP = false>
@@ -272,17 +272,17 @@ __global__ void __launch_bounds__(256) k_finalize_b(const RepCore* __restrict__ 
     finalize_body<LEAN>(F);
 }
 
-template <typename R>
-__global__ void __launch_bounds__(256) k_forces_fused_b(const RepNb<R>* __restrict__ rnb, const RepCore* __restrict__ reps, AlchDyn da, BondedDyn db, int nb1, int nb2) {
+template <typename R, bool SW = false>
+__global__ void __launch_bounds__(256) k_forces_fused_b(const RepNb<R>* __restrict__ rnb, const RepCore* __restrict__ reps, AlchDyn da, BondedDyn db, int nb1, int nb2, LjSw sw) {
     if (!reps[blockIdx.y].active) return;
     const int b = blockIdx.x;
     if (b < nb1) {
         const RepNb<R>& rp = rnb[blockIdx.y];
         const NbArgs<R> a = rp.nb; const NbConst<R> c = rp.c;
-        nonbonded_body<R, false, 4>(a, c, rp.img, b);
+        nonbonded_body<R, false, 4, SW>(a, c, rp.img, b, sw);
         return;
     }
-    if (b < nb1 + nb2) { AlchArgs A = reps[blockIdx.y].al; apply_dyn(A, da); alchemical_body<sizeof(R) == 4>(A, b - nb1); return; }
+    if (b < nb1 + nb2) { AlchArgs A = reps[blockIdx.y].al; apply_dyn(A, da); alchemical_body<sizeof(R) == 4, -1, 0, SW>(A, b - nb1, sw); return; }
     BondedArgs B = reps[blockIdx.y].bo; apply_dyn(B, db, reps[blockIdx.y].draw_delta);
     bonded_entries_body(B, b - nb1 - nb2, 256);
 }
@@ -451,10 +451,10 @@ __global__ void __launch_bounds__(256) k_frozen_boxes_b(const RepNb<R>* __restri
     const RepNb<R>& rp = rnb[work[blockIdx.y]];
     frozen_boxes_body<R>(rp.L.n, rp.c, rp.img, reinterpret_cast<FrozenBox<R>*>(rp.nb.epart + off_frozen + 2 * ((rp.L.n + FROZEN_TILE - 1) / FROZEN_TILE)), blockIdx.x);
 }
-template <typename R>
-__global__ void __launch_bounds__(256) k_energy_frozen_b(const RepNb<R>* __restrict__ rnb, const int* __restrict__ work, int off_frozen) {
+template <typename R, bool SW = false>
+__global__ void __launch_bounds__(256) k_energy_frozen_b(const RepNb<R>* __restrict__ rnb, const int* __restrict__ work, int off_frozen, LjSw sw) {
     const RepNb<R>& rp = rnb[work[blockIdx.y]];
-    energy_frozen_body<R>(rp.L.n, rp.c, rp.img, rp.L.ex_start, rp.L.ex_idx, rp.nb.epart + off_frozen, blockIdx.x);
+    energy_frozen_body<R, SW>(rp.L.n, rp.c, rp.img, rp.L.ex_start, rp.L.ex_idx, rp.nb.epart + off_frozen, blockIdx.x, sw);
 }
 template <typename R>
 __global__ void __launch_bounds__(64) k_sum_frozen_b(const RepNb<R>* __restrict__ rnb, const int* __restrict__ work, int count, int off_frozen, int nfb, double* __restrict__ out) {

@@ -337,8 +337,8 @@ __device__ __forceinline__ void frag_lists_body(const FragArgs& fa, const int fo
 // REL: a pair's separation from the j-atom's offset to the fragment's FIRST atom (one fixed-point minimum image per j-atom and
 // chunk) plus the i-atom's offset inside its fragment -- valid where cutoff + the fragment's reach stays below half the shortest
 // box edge (the host chooses; the kernel checks every fragment).  Otherwise the fixed-point difference per pair.
-template <bool ENERGY, bool REL>
-__device__ __forceinline__ void nonbonded_frag_body(const FragArgs& fa, const NbConst<float>& c, const int wg) {
+template <bool ENERGY, bool REL, bool SW = false>   // SW: the Lennard-Jones switching function (device_common.h)
+__device__ __forceinline__ void nonbonded_frag_body(const FragArgs& fa, const NbConst<float>& c, const int wg, const LjSw& sw) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4))); typedef float f32x2 __attribute__((ext_vector_type(2)));
     __shared__ f32x2 s_lj[FR_TYPES_MAX];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -355,6 +355,8 @@ __device__ __forceinline__ void nonbonded_frag_body(const FragArgs& fa, const Nb
     float k_wa = c.ew.wa, k_nbig = -1073741824.0f, k_bigrc2 = c.rc2 * 1073741824.0f, k_sx = c.scale[0], k_sy = c.scale[1], k_sz = c.scale[2], k_far = 4.0f * c.rc2;
     FR_VREG(k_wa); FR_VREG(k_nbig); FR_VREG(k_bigrc2); FR_VREG(k_sx); FR_VREG(k_sy); FR_VREG(k_sz); FR_VREG(k_far);
     const bool exact = c.ew.exact != 0;
+    float k_rs = 0.0f, k_iw = 0.0f;   // (SW only: the unswitched instantiation does not read the argument)
+    if constexpr (SW) { k_rs = (float)sw.rs; k_iw = (float)sw.iw; FR_VREG(k_rs); FR_VREG(k_iw); }
     double elj = 0.0, ecl = 0.0;
     const int w = wg * (FR_THREADS / 64) + wv;
     const int q0 = w * fa.fpw, q1 = min(fa.NI, q0 + fa.fpw);
@@ -441,7 +443,12 @@ __device__ __forceinline__ void nonbonded_frag_body(const FragArgs& fa, const Nb
                 if (LJ) {
                     const float sig = ihs[a] + jl.x;
                     const float s2 = sig * sig * inv_r2, s6 = s2 * s2 * s2, tt = (ise[a] * jl.y) * s6;
-                    const float flj = tt * fmaf(12.0f, s6, -6.0f);
+                    float flj = tt * fmaf(12.0f, s6, -6.0f);
+                    if constexpr (SW) {   // U S and fs S - U S' / r of the 12-6 term (flj is multiplied by 1 / r^2: -U S' / r enters as -U S' r)
+                        const float u = tt * (s6 - 1.0f);
+                        float dS; const float sm1 = lj_switch_m1<float>(r2 * inv_r, k_rs, k_iw, &dS);
+                        flj = fmaf(flj, sm1, fmaf(-u * dS, r2 * inv_r, flj));
+                    }
                     fs = fmaf(flj, inv_r2, fs);
                 }
                 float m;   // 1 inside the cutoff, 0 outside: (rc^2 - r^2) 2^30 clamped to [0, 1]
@@ -450,7 +457,7 @@ __device__ __forceinline__ void nonbonded_frag_body(const FragArgs& fa, const Nb
                 fx[a] = fmaf(fs, dx, fx[a]); fy[a] = fmaf(fs, dy, fy[a]); fz[a] = fmaf(fs, dz, fz[a]);
             } else if (r2 < c.rc2) {
                 float e1, e2;
-                pair_regular<float>(r2, iq[a] * jq, ihs[a] + jl.x, ise[a] * jl.y, c, &e1, &e2);
+                pair_regular_s<float, SW>(r2, iq[a] * jq, ihs[a] + jl.x, ise[a] * jl.y, c, sw, &e1, &e2);
                 elj += (double)(jw * e1); ecl += (double)(jw * e2);   // jw: 1/2 where the partner is mobile too (that pair is met from both sides), 1 for a frozen one
             }
         };
@@ -531,9 +538,9 @@ __global__ void __launch_bounds__(FR_THREADS) k_frag_boxes(FragArgs fa, const At
 __global__ void __launch_bounds__(FR_THREADS) k_frag_lists(FragArgs fa, int force) {
     frag_lists_body(fa, force, blockIdx.x);
 }
-template <bool ENERGY, bool REL>
-__global__ void __launch_bounds__(FR_THREADS) k_nonbonded_frag(FragArgs fa, NbConst<float> c) {
-    nonbonded_frag_body<ENERGY, REL>(fa, c, blockIdx.x);
+template <bool ENERGY, bool REL, bool SW = false>
+__global__ void __launch_bounds__(FR_THREADS) k_nonbonded_frag(FragArgs fa, NbConst<float> c, LjSw sw) {
+    nonbonded_frag_body<ENERGY, REL, SW>(fa, c, blockIdx.x, sw);
 }
 
 // Audit (diagnostic; blues_audit_lists): one block per i-fragment.  Every atom of the system within the cutoff of one of the

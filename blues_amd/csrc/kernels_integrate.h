@@ -998,12 +998,12 @@ __global__ void k_gather_forces(IntArgs A, int slot, double* out /*[n][3]*/) {
 // The three force kernels of a pass are independent of each other; when the i-set is small they are all
 // latency-bound, so one launch with block-role dispatch runs them side by side on different CUs and saves
 // two kernel boundaries:  blocks [0,nb1) nonbonded | [nb1,nb1+nb2) alchemical | the rest bonded entries + noise.
-template <typename R>
+template <typename R, bool SW = false>
 __global__ void __launch_bounds__(256) k_forces_fused(NbArgs<R> a, NbConst<R> c, const typename Img<R>::Atom* __restrict__ img,
-                                                      AlchArgs A, BondedArgs B, int nb1, int nb2) {
+                                                      AlchArgs A, BondedArgs B, int nb1, int nb2, LjSw sw) {
     const int b = blockIdx.x;
-    if (b < nb1) { nonbonded_body<R, false, 4>(a, c, img, b); return; }
-    if (b < nb1 + nb2) { alchemical_body<sizeof(R) == 4>(A, b - nb1); return; }
+    if (b < nb1) { nonbonded_body<R, false, 4, SW>(a, c, img, b, sw); return; }
+    if (b < nb1 + nb2) { alchemical_body<sizeof(R) == 4, -1, 0, SW>(A, b - nb1, sw); return; }
     bonded_entries_body(B, b - nb1 - nb2, 256);
 }
 

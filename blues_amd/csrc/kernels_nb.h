@@ -680,8 +680,8 @@ template <typename R> struct NbArgs {
 
 // One block = WPB waves working on the SAME i-tile; wave w of the tile walks the j-list segments
 // q = w, w+NW, w+2NW, ...; the block's waves are summed through LDS into one partial slab.
-template <typename R, bool ENERGY, int WPB>
-__device__ __forceinline__ void nonbonded_body(const NbArgs<R>& a, const NbConst<R>& c, const typename Img<R>::Atom* __restrict__ img, const int block_id) {
+template <typename R, bool ENERGY, int WPB, bool SW = false>   // SW: the Lennard-Jones switching function (device_common.h: pair_regular_s)
+__device__ __forceinline__ void nonbonded_body(const NbArgs<R>& a, const NbConst<R>& c, const typename Img<R>::Atom* __restrict__ img, const int block_id, const LjSw& sw) {
     using Atom = typename Img<R>::Atom;
     using sfix = typename Img<R>::sfix;
     __shared__ Atom lds[WPB][64];
@@ -722,7 +722,7 @@ __device__ __forceinline__ void nonbonded_body(const NbArgs<R>& a, const NbConst
             bool in = (r2 < c.rc2) && !((m >> k) & 1ull);
             if (in) {
                 R e1, e2;
-                R fs = pair_regular<R>(r2, ai.q * bj.q, ai.hs + bj.hs, ai.se * bj.se, c, &e1, &e2);
+                R fs = pair_regular_s<R, SW>(r2, ai.q * bj.q, ai.hs + bj.hs, ai.se * bj.se, c, sw, &e1, &e2);
                 fx += (double)(fs * dx); fy += (double)(fs * dy); fz += (double)(fs * dz);
                 if (ENERGY) {
                     double wgt = (bj.flags & FLAG_MOBILE) ? 0.5 : 1.0;
@@ -748,9 +748,9 @@ __device__ __forceinline__ void nonbonded_body(const NbArgs<R>& a, const NbConst
     }
 }
 
-template <typename R, bool ENERGY, int WPB>
-__global__ void __launch_bounds__(WPB * 64) k_nonbonded(NbArgs<R> a, NbConst<R> c, const typename Img<R>::Atom* __restrict__ img) {
-    nonbonded_body<R, ENERGY, WPB>(a, c, img, blockIdx.x);
+template <typename R, bool ENERGY, int WPB, bool SW = false>
+__global__ void __launch_bounds__(WPB * 64) k_nonbonded(NbArgs<R> a, NbConst<R> c, const typename Img<R>::Atom* __restrict__ img, LjSw sw) {
+    nonbonded_body<R, ENERGY, WPB, SW>(a, c, img, blockIdx.x, sw);
 }
 
 // ---- throughput variant for large i-sets (mixed precision): a wave owns a SUB-tile of IW i-atoms and JL = 64/IW
@@ -758,8 +758,8 @@ __global__ void __launch_bounds__(WPB * 64) k_nonbonded(NbArgs<R> a, NbConst<R> 
 // VALU ops) runs for all 64 lanes although only ~23 % of the pairs are inside the cutoff; with 8 i-atoms x 8
 // consecutive (Hilbert-sorted) j-atoms many wave-iterations have no pair in range and are skipped by the exec-mask
 // branch.  j-batches are staged in a wave-private, bank-conflict-free LDS image ({x,y,z,q} 16 B + {hs,se} 8 B).
-template <bool ENERGY, int IW>
-__device__ __forceinline__ void nonbonded_sub_body(const NbArgs<float>& a, const NbConst<float>& c, const AtomF* __restrict__ img, const int block_id) {
+template <bool ENERGY, int IW, bool SW = false>
+__device__ __forceinline__ void nonbonded_sub_body(const NbArgs<float>& a, const NbConst<float>& c, const AtomF* __restrict__ img, const int block_id, const LjSw& sw) {
     constexpr int JL = 64 / IW, SUBS = 64 / IW;
     struct P4 { uint32_t x, y, z; float q; };
     struct P2 { float hs, se; };
@@ -812,7 +812,7 @@ __device__ __forceinline__ void nonbonded_sub_body(const NbArgs<float>& a, const
             if (in) {
                 const P2 bp = mq[k];
                 float e1, e2;
-                float fs = pair_regular<float>(r2, ai.q * bj.q, ai.hs + bp.hs, ai.se * bp.se, c, &e1, &e2);
+                float fs = pair_regular_s<float, SW>(r2, ai.q * bj.q, ai.hs + bp.hs, ai.se * bp.se, c, sw, &e1, &e2);
                 bx = fmaf(fs, dx, bx); by = fmaf(fs, dy, by); bz = fmaf(fs, dz, bz);
                 if (ENERGY) {
                     const double wgt = (mf[k] & FLAG_MOBILE) ? 0.5 : 1.0;
@@ -836,9 +836,9 @@ __device__ __forceinline__ void nonbonded_sub_body(const NbArgs<float>& a, const
     }
 }
 
-template <bool ENERGY, int IW>
-__global__ void __launch_bounds__(256) k_nonbonded_sub(NbArgs<float> a, NbConst<float> c, const AtomF* __restrict__ img) {
-    nonbonded_sub_body<ENERGY, IW>(a, c, img, blockIdx.x);
+template <bool ENERGY, int IW, bool SW = false>
+__global__ void __launch_bounds__(256) k_nonbonded_sub(NbArgs<float> a, NbConst<float> c, const AtomF* __restrict__ img, LjSw sw) {
+    nonbonded_sub_body<ENERGY, IW, SW>(a, c, img, blockIdx.x, sw);
 }
 
 // ---- per-atom Verlet lists + LDS-resident tile image (mixed precision; the kernel of the replica-batched benchmark path).
@@ -897,8 +897,8 @@ __global__ void __launch_bounds__(256) k_nonbonded_sub(NbArgs<float> a, NbConst<
 // group: 33 VALU instructions and one DS read instead of 43 and two.  The force kernel's polynomial form only: six
 // walks ({prune} x {LJ} and the two erfc/exp walks), 51 KB of code; the energy kernel is the one it was.  NbArgs.coulomb_walk = 0
 // (blues_set_global "nb_coulomb_walk"): every atom takes the full walk.
-template <bool ENERGY>
-__device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, const NbConst<float>& c, const AtomF* __restrict__ img, const int t) {   // t: list (group of S i-tiles)
+template <bool ENERGY, bool SW = false>
+__device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, const NbConst<float>& c, const AtomF* __restrict__ img, const int t, const LjSw& sw) {   // t: list (group of S i-tiles)
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4))); typedef float f32x4 __attribute__((ext_vector_type(4))); typedef float f32x2 __attribute__((ext_vector_type(2)));   // (plain vector types: loads through an address-space pointer stay loads)
     extern __shared__ __align__(16) unsigned char nb_smem[];   // (the kernel has NO static LDS: the dynamic area then starts at address 0 and a list entry IS an LDS address)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
@@ -1035,6 +1035,8 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
     NB_VREG(k_wa); NB_VREG(k_nbig); NB_VREG(k_bigrc2); NB_VREG(k_sx); NB_VREG(k_sy); NB_VREG(k_sz);
     float k_rp2 = c.rp2, k_rp2m = c.rp2_m;   // (a select between two fields of the argument record becomes an indexed load from a scratch copy of it)
     NB_VREG(k_rp2); NB_VREG(k_rp2m);
+    float k_rs = 0.0f, k_iw = 0.0f;   // the Lennard-Jones switch (SW only: the unswitched instantiation does not read the argument)
+    if constexpr (SW) { k_rs = (float)sw.rs; k_iw = (float)sw.iw; NB_VREG(k_rs); NB_VREG(k_iw); }
     const bool exact = c.ew.exact != 0;   // (kernel argument: wave-uniform)
     // (the Coulomb-only walk exists for the force kernel's polynomial form; NbArgs.coulomb_walk = 0: every atom takes the full walk)
 #if defined(K1X_EMPTY) || defined(K1X_NOPOLY) || defined(K1X_NOGATHER) || defined(K1X_NOCVT) || defined(K1X_NOLIST) || defined(K1X_NOREDUCE)
@@ -1101,6 +1103,11 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
                     const float sig = ihs + __builtin_fabsf(q2.x);
                     const float s2 = sig * sig * inv_r2, s6 = s2 * s2 * s2, tt = (ise * q2.y) * s6;
                     flj = tt * fmaf(12.0f, s6, -6.0f);
+                    if constexpr (SW) {   // U S and fs S - U S' / r of the 12-6 term; flj is multiplied by 1 / r^2 below, so -U S' / r enters as -U S' r
+                        const float u = tt * (s6 - 1.0f);
+                        float dS; const float sm1 = lj_switch_m1<float>(r2 * inv_r, k_rs, k_iw, &dS);
+                        flj = fmaf(flj, sm1, fmaf(-u * dS, r2 * inv_r, flj));
+                    }
                 }
                 float g;
                 if (X) {
@@ -1126,7 +1133,7 @@ __device__ __forceinline__ void nonbonded_atom_body(const NbArgs<float>& a, cons
                 bx = fmaf(fs, dx, bx); by = fmaf(fs, dy, by); bz = fmaf(fs, dz, bz);
             } else if (r2 < c.rc2) {
                 float e1, e2;
-                pair_regular<float>(r2, iq * jq, ihs + __builtin_fabsf(q2.x), ise * q2.y, c, &e1, &e2);
+                pair_regular_s<float, SW>(r2, iq * jq, ihs + __builtin_fabsf(q2.x), ise * q2.y, c, sw, &e1, &e2);
                 const double wgt = __builtin_bit_cast(int, q2.x) < 0 ? 0.5 : 1.0;   // a mobile j meets this pair again from its own list
                 elj += wgt * (double)e1; ecl += wgt * (double)e2;
             }
@@ -1278,9 +1285,9 @@ __global__ void __launch_bounds__(256) k_audit_atom_lists(NbArgs<float> a, ListA
     if (missing) atomicAdd(&out[1], missing);
 }
 
-template <bool ENERGY>
-__global__ void __launch_bounds__(1024) k_nonbonded_atom(NbArgs<float> a, NbConst<float> c, const AtomF* __restrict__ img) {
-    nonbonded_atom_body<ENERGY>(a, c, img, blockIdx.x);
+template <bool ENERGY, bool SW = false>
+__global__ void __launch_bounds__(1024) k_nonbonded_atom(NbArgs<float> a, NbConst<float> c, const AtomF* __restrict__ img, LjSw sw) {
+    nonbonded_atom_body<ENERGY, SW>(a, c, img, blockIdx.x, sw);
 }
 
 // One-off: LJ + Coulomb energy among FROZEN environment atoms (constant while they and the box stay put).
@@ -1325,9 +1332,9 @@ __device__ __forceinline__ void frozen_boxes_body(const int n, const NbConst<R>&
     if (lane == 0) { FrozenBox<R> B; for (int k = 0; k < 3; k++) { B.c[k] = cf[k]; B.h[k] = hf[k]; } B.any = any ? 1 : 0; boxes[it] = B; }
 }
 
-template <typename R>
+template <typename R, bool SW = false>
 __device__ __forceinline__ void energy_frozen_body(const int n, const NbConst<R>& c, const typename Img<R>::Atom* __restrict__ img,
-                                                   const int* __restrict__ ex_start, const int* __restrict__ ex_idx, double* epart, const int it) {
+                                                   const int* __restrict__ ex_start, const int* __restrict__ ex_idx, double* epart, const int it, const LjSw& sw) {
     using Atom = typename Img<R>::Atom;
     using sfix = typename Img<R>::sfix;
     using ufix = typename Img<R>::ufix;
@@ -1390,7 +1397,7 @@ __device__ __forceinline__ void energy_frozen_body(const int n, const NbConst<R>
                     for (int e = e0; e < e1; e++) ex |= (ex_idx[e] == jj);
                     if (!ex) {
                         R a1, a2;
-                        pair_regular<R>(r2, ai.q * bj.q, ai.hs + bj.hs, ai.se * bj.se, c, &a1, &a2);
+                        pair_regular_s<R, SW>(r2, ai.q * bj.q, ai.hs + bj.hs, ai.se * bj.se, c, sw, &a1, &a2);
                         elj += (double)a1; ecl += (double)a2;
                     }
                 }
@@ -1412,10 +1419,10 @@ template <typename R>
 __global__ void __launch_bounds__(256) k_frozen_boxes(int n, NbConst<R> c, const typename Img<R>::Atom* __restrict__ img, double* epart) {
     frozen_boxes_body<R>(n, c, img, reinterpret_cast<FrozenBox<R>*>(epart + 2 * ((n + FROZEN_TILE - 1) / FROZEN_TILE)), blockIdx.x);
 }
-template <typename R>
+template <typename R, bool SW = false>
 __global__ void __launch_bounds__(256) k_energy_frozen(int n, NbConst<R> c, const typename Img<R>::Atom* __restrict__ img,
-                                                       const int* __restrict__ ex_start, const int* __restrict__ ex_idx, double* epart) {
-    energy_frozen_body<R>(n, c, img, ex_start, ex_idx, epart, blockIdx.x);
+                                                       const int* __restrict__ ex_start, const int* __restrict__ ex_idx, double* epart, LjSw sw) {
+    energy_frozen_body<R, SW>(n, c, img, ex_start, ex_idx, epart, blockIdx.x, sw);
 }
 
 __device__ inline void to_fixed32(const double p[3], const Box3& box, unsigned u[3]);

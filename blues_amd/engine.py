@@ -30,6 +30,7 @@ class NativeEngine:
             system.check_charmm()
         except ValueError as e:
             raise EngineError(str(e))
+        system.check_switch_distance()   # (ValueError, as from system_from_amber and with_switch_distance)
         self._lib = load()
         sd, self._keep_s = system.to_desc()
         idesc, self._keep_i = integrator.to_desc()
@@ -37,6 +38,9 @@ class NativeEngine:
         ext = system.ext_desc()
         if ext is not None:
             # (additive entry point: a library built before it loads, and only a System that needs it says so)
+            if isinstance(ext, _abi.BluesSystemExtV4) and not hasattr(self._lib, "blues_get_lj_switch"):
+                raise EngineError("a System with a Lennard-Jones switch (switch_distance %g nm) needs BluesSystemExtV4 and blues_get_lj_switch, which "
+                                  "this library does not have: rebuild it (python -m blues_amd.build)" % (system.switch_distance,))
             if not hasattr(self._lib, "blues_engine_create_ext"):
                 raise EngineError("alchemical_pme_treatment %r needs blues_engine_create_ext, which this library does not have: rebuild it "
                                   "(python -m blues_amd.build)" % (system.alchemical_pme_treatment,))
@@ -234,6 +238,15 @@ class NativeEngine:
                 "max_jcount": s[8], "resorts": s[9], "list_builds": s[10], "own_energy_evaluations": s[11],
                 "nonbonded_kernel": s[12], "tiles_per_list": s[13], "atom_list_entries": s[14], "atom_list_iterations": s[15],
                 "atom_prunes": s[16], "pruned_list_entries": s[17], "pruned_list_iterations": s[18], "pruned_lists": s[19], "alchemical_kernel": s[20], "step_threads": s[21]}
+
+    def lj_switch(self):
+        """(switch distance in force in nm -- 0.0 when none --, pair-kernel launches that ran in their switched instantiation so far)
+        (include/blues_engine.h: blues_get_lj_switch); (0.0, 0) from a library without the entry, which knows no switch."""
+        if not hasattr(self._lib, "blues_get_lj_switch"):
+            return 0.0, 0
+        out = (C.c_double * 2)()
+        self._check(self._lib.blues_get_lj_switch(self._h, out))
+        return float(out[0]), int(out[1])
 
     def alchemical_layout(self):
         """(PA, k2_jiter, entries of the alchemical j-list at the last build, entries of the alchemical exception rows): the shape the

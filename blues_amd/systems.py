@@ -22,6 +22,7 @@ _ARRAY_FIELDS = ("box", "mass", "charge", "sigma", "epsilon", "exclusions", "exc
 _SCALAR_FIELDS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha",
                   "annihilate_electrostatics", "annihilate_sterics", "remove_cm_motion")
 _OPTIONAL_SCALARS = ("pme_order", "dispersion_correction")   # (files written before reciprocal space existed do not have them)
+_LJ_SWITCH_GL = np.polynomial.legendre.leggauss(32)   # the rule of blues_engine.hip: lj_switch_shell_integrals
 _CHARMM_FIELDS = ("urey_bradley_atoms", "urey_bradley_params", "improper_atoms", "improper_params")   # SystemData's Urey-Bradley terms and impropers
 _GB_FIELDS = ("model", "radius", "scale", "solute_dielectric", "solvent_dielectric", "surface_area_energy")   # SystemData.implicit_solvent, stored as gb_<field>
 
@@ -40,6 +41,8 @@ def save_system(path, system: SystemData, **extra):
         d.update({"cmap_map_%d" % k: np.asarray(m, dtype=np.float64) for k, m in enumerate(system.cmap_maps)})
     if system.has_charmm:   # (likewise)
         d.update({k: np.asarray(getattr(system, k)) for k in _CHARMM_FIELDS})
+    if float(system.switch_distance) != 0.0:   # (likewise)
+        d["switch_distance"] = np.asarray(float(system.switch_distance))
     d.update({k: np.asarray(v) for k, v in extra.items()})
     np.savez_compressed(path, **d)
 
@@ -64,6 +67,8 @@ def load_system(path):
         kw["cmap_maps"] = tuple(z["cmap_map_%d" % k] for k in range(int(z["cmap_n_maps"])))
         kw["cmap_torsions"] = z["cmap_torsions"]
     kw.update({k: z[k] for k in _CHARMM_FIELDS if k in z.files})
+    if "switch_distance" in z.files:   # (older files: 0, no switch)
+        kw["switch_distance"] = float(z["switch_distance"].item())
     extra = {k: z[k] for k in z.files if k not in kw and not k.startswith("gb_") and not k.startswith("cmap_")}
     return SystemData(**kw), extra
 
@@ -100,6 +105,15 @@ def with_alchemical_pme_treatment(system: SystemData, treatment):
     s = copy.copy(system)
     s.alchemical_pme_treatment = treatment
     s.check_alchemical_pme_treatment()
+    return s
+
+
+def with_switch_distance(system: SystemData, distance):
+    """The same System with createSystem's switchDistance (reference blues/simulation.py:157-161, blues/settings.py:155): the Lennard-Jones
+    switching function between `distance` (nm) and the cutoff.  0 or a value >= the cutoff: no switch; negative or not finite: ValueError."""
+    s = copy.copy(system)
+    s.switch_distance = float(distance)
+    s.check_switch_distance()
     return s
 
 
@@ -203,6 +217,7 @@ def tile_system(system: SystemData, reps):
         cmap_maps=tuple(system.cmap_maps or ()), cmap_torsions=_tile_cmap_torsions(system.cmap_torsions, n, ncopy),
         urey_bradley_atoms=rep_idx(system.urey_bradley_atoms), urey_bradley_params=rep_val(system.urey_bradley_params),
         improper_atoms=rep_idx(system.improper_atoms), improper_params=rep_val(system.improper_params),
+        switch_distance=system.switch_distance,
     )
 
 
@@ -328,7 +343,7 @@ def assemble_s23k_solute(base: SystemData, vel, removed_waters, inserted_x, inse
         remove_cm_motion=base.remove_cm_motion, pme_order=base.pme_order, dispersion_correction=base.dispersion_correction, positions=pos,
         residue_of_atom=new_res.astype(np.int32), alchemical_pme_treatment=base.alchemical_pme_treatment,
         urey_bradley_atoms=ub_a.reshape(-1, 2), urey_bradley_params=np.asarray(ub_p, np.float64).reshape(-1, 2),
-        improper_atoms=imp_a.reshape(-1, 4), improper_params=np.asarray(imp_p, np.float64).reshape(-1, 2))
+        improper_atoms=imp_a.reshape(-1, 4), improper_params=np.asarray(imp_p, np.float64).reshape(-1, 2), switch_distance=base.switch_distance)
     assert s.n_atoms == n
     return s, v
 
@@ -354,9 +369,12 @@ ONE_4PI_EPS0 = 138.935456
 
 
 def dispersion_correction_energy(system: SystemData, zero_epsilon=()):
-    """OpenMM's long-range dispersion correction of a NonbondedForce with the cutoff and no switching function, in the form the engine
-    and the oracle use (blues_engine.hip: pme_tables; oracle/blues_oracle.c: dispersion_correction) [recalled: NonbondedForceImpl::
-    calcDispersionCorrection]; the atoms in `zero_epsilon` enter with epsilon 0 (disable_alchemical_dispersion_correction=True)."""
+    """OpenMM's long-range dispersion correction of a NonbondedForce with the cutoff, in the form the engine and the oracle use
+    (blues_engine.hip: pme_tables; oracle/blues_oracle.c: dispersion_correction) [recalled: NonbondedForceImpl::
+    calcDispersionCorrection]; the atoms in `zero_epsilon` enter with epsilon 0 (disable_alchemical_dispersion_correction=True).
+    With a switching function in force (SystemData.lj_switch_in_force: rs) the pairs of the shell rs < r < rc keep U S, and the correction
+    gains the integral of r^2 U (1 - S) over it: sigma^12 I12 - sigma^6 I6 per class with the same weights, I12 and I6 by the engine's
+    fixed 32-point Gauss-Legendre rule.  Without one the value is the closed form it always was, bit for bit."""
     n = system.n_atoms
     eps = np.array(system.epsilon, dtype=np.float64)
     eps[np.asarray(zero_epsilon, dtype=np.int64)] = 0.0
@@ -371,12 +389,21 @@ def dispersion_correction_energy(system: SystemData, zero_epsilon=()):
     tot = 0.5 * n * (n + 1.0)
     rc3 = system.cutoff ** 3; rc9 = rc3 ** 3
     V = float(np.prod(np.asarray(system.box, dtype=np.float64).reshape(-1)[:3]))
-    return 8.0 * n * float(n) * np.pi * (s12 / tot / (9.0 * rc9) - s6 / tot / (3.0 * rc3)) / V
+    rs = system.lj_switch_in_force
+    if rs == 0.0:
+        return 8.0 * n * float(n) * np.pi * (s12 / tot / (9.0 * rc9) - s6 / tot / (3.0 * rc3)) / V
+    rc = float(system.cutoff)
+    t, w = _LJ_SWITCH_GL
+    r = 0.5 * (rc + rs) + 0.5 * (rc - rs) * t
+    x = (r - rs) / (rc - rs)
+    one_minus_s = x ** 3 * (10.0 + x * (-15.0 + 6.0 * x))
+    i12 = 0.5 * (rc - rs) * float((w * one_minus_s / r ** 10).sum()); i6 = 0.5 * (rc - rs) * float((w * one_minus_s / r ** 4).sum())
+    return 8.0 * n * float(n) * np.pi * (s12 / tot * (1.0 / (9.0 * rc9) + i12) - s6 / tot * (1.0 / (3.0 * rc3) + i6)) / V
 
 
 _FORCE_FIELD_ARRAYS = ("charge", "sigma", "epsilon", "exclusions", "exception_atoms", "exception_params", "bond_atoms", "bond_params", "angle_atoms",
                        "angle_params", "torsion_atoms", "torsion_params", "restraint_atoms", "restraint_x0") + _CHARMM_FIELDS
-_FORCE_FIELD_SCALARS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha", "pme_order", "dispersion_correction")
+_FORCE_FIELD_SCALARS = ("restraint_k", "nonbonded_method", "cutoff", "ewald_alpha", "softcore_alpha", "pme_order", "dispersion_correction", "switch_distance")
 
 
 def same_implicit_solvent(a, b):

@@ -270,7 +270,36 @@ typedef struct BluesSystemExtV3 {
     const int32_t *improper_atoms;       /* [4 * n_impropers] */
     const double *improper_params;       /* [2 * n_impropers] psi0, k */
 } BluesSystemExtV3;
-/* ext = NULL: blues_engine_create_gb; ext->struct_size says which of the two structs (or the 8-byte head) ext points to */
+/* The Lennard-Jones switching function of a periodic System (createSystem's switchDistance; OpenMM's NonbondedForce.setUseSwitchingFunction /
+ * setSwitchingDistance, which openmmtools copies onto its alchemical forces).  Additive to ABI 9: BluesSystemExtV3 grown at its end.
+ * With rs = lj_switch_distance, rc = the cutoff and x = (r - rs) / (rc - rs) clamped to [0, 1],
+ *     S = 1 - 10 x^3 + 15 x^4 - 6 x^5,
+ * every non-excluded pair inside the cutoff has its 12-6 energy -- or the softcore / plain sterics of a pair with an alchemical atom, in
+ * every lambda slot -- multiplied by S, and its force scale becomes fs S - U S' / r.  Coulomb in any form, the exceptions (alchemical
+ * rows included), the mesh and the bonded terms are not switched.  The dispersion correction gains the integral of r^2 U (1 - S) over
+ * rs < r < rc.  0, or a value >= the cutoff: no switch (the kernels an engine without this struct runs); on a NoCutoff System the value
+ * is ignored.  Negative or not finite: refused.  An older struct_size means no switch.
+ * lj_switch_reserved must be 0; it also keeps sizeof(BluesSystemExtV4) away from sizeof(BluesSystemExtV3) + 8, a struct_size this
+ * library has always refused by name. */
+typedef struct BluesSystemExtV4 {
+    int32_t struct_size;                 /* sizeof(BluesSystemExtV4) */
+    int32_t alchemical_pme_treatment;
+    int32_t n_cmap_maps;
+    const int32_t *cmap_size;
+    const double *cmap_energy;
+    int32_t n_cmap_torsions;
+    const int32_t *cmap_torsion_map;
+    const int32_t *cmap_torsion_atoms;
+    int32_t n_urey_bradley;
+    const int32_t *urey_bradley_atoms;
+    const double *urey_bradley_params;
+    int32_t n_impropers;
+    const int32_t *improper_atoms;
+    const double *improper_params;
+    double lj_switch_distance;           /* nm (offset sizeof(BluesSystemExtV3)) */
+    double lj_switch_reserved;           /* 0 */
+} BluesSystemExtV4;
+/* ext = NULL: blues_engine_create_gb; ext->struct_size says which of the three structs (or the 8-byte head) ext points to */
 int blues_engine_create_ext(const BluesSystemDesc *sys, const BluesIntegratorDesc *integ, const BluesImplicitSolventDesc *gb, const BluesSystemExt *ext, int device, BluesEngine **out);
 /* (phi, psi) of every CMAP torsion at the engine's current device positions, radians in [0, 2 pi): what a Ramachandran reporter
  * reads.  Additive to ABI 9; a library without it loads, and only a System with maps needs it. */
@@ -447,6 +476,10 @@ int blues_get_exact_pme_path(BluesEngine *h, int64_t out[2]);
  * The static launch of the frozen charges is not counted.  Zeros without reciprocal space.  blues_get_global("pme_fast_launches") and
  * ("pme_general_launches") give one word each.  Additive (BLUES_ABI_VERSION unchanged). */
 int blues_get_pme_path(BluesEngine *h, int64_t out[2]);
+/* The Lennard-Jones switch of this engine: out[0] the switch distance in force, nm (0: none), out[1] how many pair-kernel launches have
+ * run in their switched instantiation so far (0 on an engine without a switch: it launches the kernels it always has).  Additive to ABI 9;
+ * a library without it loads. */
+int blues_get_lj_switch(BluesEngine *h, double out[2]);
 /* the shape the alchemical kernels run in, read from the host's layout (no launch): [0] PA, the alchemical region's size padded to a
  * power of two (the lane layout is (j-slot, a) with 256 / PA j-slots per block) [1] k2_jiter, the j-groups an environment block
  * walks, after its clamp to PA (1 << 20 under the dense form: one logical block) [2] entries of the alchemical atoms' j-list at the
